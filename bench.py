@@ -1,6 +1,9 @@
 """Headline benchmark: processed edges/sec (fwd+bwd) on flag_simple-shape meshes (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+        K timed steps after W warm-up steps; `ms_per_step` in the JSON line is the time of one timed step.
+        --dump-outputs DIR: the last timed step's loss, updated parameters and gradients as DIR/*.npy (inputs are seeded, so
+        two builds run with the same arguments can be compared output for output).
         N>1 without WORLD_SIZE in the environment: this process starts `python -m torch.distributed.run --nproc-per-node N
         bench.py ...` as a CHILD (before anything touches the GPU) and exits with its code; under torch.distributed.run
         (WORLD_SIZE set) it is one rank of the job: one process per GPU, RCCL over xGMI.
@@ -109,7 +112,36 @@ def parse():
                     help='one rank, but through the N>1 code path: RCCL communicator of one rank, forward+backward replayed (or eager with '
                          'bucketed all-reduces), collective + scaling + Adam eager -- what a rank of the multi-GPU job runs besides waiting for its peers')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): loss, the '
+                         'parameters after its Adam update and the gradients it applied (rank 0; see dump_outputs)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20       # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: one float32 DIR/<name>.npy per array, flattened.  Over the budget every array keeps the same fraction of
+    its elements, chosen by a fixed seed and kept in index order, so two builds run with the same arguments compare entry for
+    entry.  -> {name: (elements written, elements computed)}"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().reshape(-1).to('cpu', torch.float32)
+        n = a.numel()
+        if frac < 1.0 and n > 1:
+            keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, int(n * frac))]
+            a = a[keep.sort().values]
+        np.save(os.path.join(out_dir, name + '.npy'), a.numpy())
+        written[name] = (a.numel(), n)
+    return written
 
 
 def kernel_source_sha() -> str:
@@ -478,6 +510,7 @@ def main():
     trainer = parallel.DataParallelTrainer(model, lr=1e-4, device_step=use_graph, wgrad_stream=args.side_stream, buckets=args.buckets,
                                            force_collectives=args.dp_rehearsal)
     n_params = trainer.fp.numel
+    init_flat = trainer.fp.flat.clone()                # the seeded initial parameters (identical on every rank after the broadcast)
 
     def barrier():
         if dp:
@@ -500,6 +533,17 @@ def main():
             log(f'HIP-graph capture failed ({type(ex).__name__}: {ex}); falling back to eager launches')
             torch.cuda.synchronize()
             use_graph = False
+    # The timed steps start from the same state in every run: the seeded initial parameters, zero Adam moments and step
+    # counters.  The warm-up only brings kernels, caches and the captured graph up; the training state it leaves behind is not
+    # reproducible from run to run (eager steps past the third differ in their last bits, which training then amplifies).
+    # In place: the captured graph keeps its addresses, and the packed weight images are rebuilt at the start of every step.
+    with torch.no_grad():
+        trainer.fp.flat.copy_(init_flat)
+        trainer.m.zero_(); trainer.v.zero_()
+        trainer.t = 0
+        if trainer.t_dev is not None:
+            trainer.t_dev.zero_()
+    trainer.ctx.invalidate_packs()
     barrier()
     log('warmup done')
     prof = not args.no_prof
@@ -511,6 +555,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     log(f'timed region done: {dt:.3f} s for {args.steps} steps')
+    if args.dump_outputs and rank == 0:      # before the profiling and cold steps below move the parameters on
+        d = dump_outputs(args.dump_outputs, {'loss': loss, 'params': trainer.fp.flat, 'grads': trainer.fp.grad})
+        log(f'outputs of the last timed step written to {args.dump_outputs}: {d}')
     if prof and use_graph:            # events cannot be recorded inside a replayed graph: short eager pass on the same buffers
         barrier()
         ops.prof_reset(); ops.prof_enable(True)

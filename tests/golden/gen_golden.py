@@ -148,6 +148,27 @@ def write_g1(a):
     torch.save(g1, os.path.join(a.out, 'g1_segment_ops.pt'))
 
 
+# Cases whose gradients are compared at 5e-5 through 15 layers (tests/test_oracle_golden.py): about 2.5 M ReLU inputs, and when
+# one of them sits within fp32 rounding of zero its gate -- and every gradient upstream of it, by 1e-3 of its scale -- depends on
+# the summation order of the CPU's BLAS.  Such a fixture holds only on CPUs that round exactly as the generating one did, so
+# the seed is the first one, counting up from the name's, whose instance is far from every kink.
+WELL_CONDITIONED = {'none_sum_L15_lat128'}
+KINK_MARGIN = 1e-6
+
+
+def well_conditioned(sd, graph, arch, agg, target, mask, grads, seed, set_order):
+    """Every ReLU input of the fp64 oracle run at least KINK_MARGIN from zero, and the reference's fp32 gradient digests
+    within a quarter of the test's tolerance of the fp64 ones."""
+    from tests import helpers as H
+    with H.KinkMargin() as km:
+        _, _, g64, _ = H.oracle_run(sd, graph, arch, agg, target, mask, set_order=set_order)
+    d32, d64 = digest(grads, seed), digest(g64, seed)
+    worst = max(float((d32[k]['proj'] - d64[k]['proj']).abs().max()) /
+                (5e-5 * float(d32[k]['l2']) * (grads[k].numel() ** 0.5) + 1e-9) for k in grads)
+    print(f'seed {seed}: kink margin {km.worst:.2e}, reference fp32 vs fp64 digests at {worst:.2f} of the tolerance')
+    return km.worst > KINK_MARGIN and worst < 0.25
+
+
 def write_models(a):
     # ---- G2-G4: model-level goldens ---------------------------------------------------------------------
     set_order = list({'mesh_edges', 'world_edges'})      # iteration order under this PYTHONHASHSEED
@@ -188,14 +209,19 @@ def write_models(a):
         cases = [c for c in cases if any(s_ in c[0] for s_ in a.only_cases.split(','))]
     for name, arch, agg, steps, sets, gkw, latent, wmode in cases:
         seed = hash_name(name) % 1000
-        graph = synth.grid_graph(seed=seed, **gkw)
-        # an edge set the model does not register must be dropped by the encoder: add one to a few cases
-        if name.startswith('none_sum_L2'):
-            extra = O.EdgeSet('unregistered', torch.randn(5, 4), torch.zeros(5, dtype=torch.long),
-                              torch.ones(5, dtype=torch.long))
-            graph = O.MultiGraph(graph.node_features, list(graph.edge_sets) + [extra])
-        sd, out, target, mask, loss, grads, in_grads = run_model(arch, agg, steps, sets, graph, latent, seed,
-                                                                 weights=wmode)
+        while True:
+            graph = synth.grid_graph(seed=seed, **gkw)
+            # an edge set the model does not register must be dropped by the encoder: add one to a few cases
+            if name.startswith('none_sum_L2'):
+                extra = O.EdgeSet('unregistered', torch.randn(5, 4), torch.zeros(5, dtype=torch.long),
+                                  torch.ones(5, dtype=torch.long))
+                graph = O.MultiGraph(graph.node_features, list(graph.edge_sets) + [extra])
+            sd, out, target, mask, loss, grads, in_grads = run_model(arch, agg, steps, sets, graph, latent, seed,
+                                                                     weights=wmode)
+            if name not in WELL_CONDITIONED or well_conditioned(sd, graph, arch, agg, target, mask, grads, seed,
+                                                                set_order + set_order_h):
+                break
+            seed += 1
         fx = {'arch': arch, 'agg': agg, 'steps': steps, 'edge_sets': sets, 'latent': latent, 'seed': seed,
               'graph_kwargs': gkw, 'set_order': set_order, 'set_order_hyper': set_order_h,
               'graph': {'node_features': graph.node_features,

@@ -136,6 +136,23 @@ def test_bench_gpus_2_starts_two_ranks():
     assert res['config']['global_batch'] == 8 and res['value'] > 0
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` on one GPU (captured step): the last timed step's loss, parameters and gradients as float32
+    .npy files -- the loss the JSON line reports, one entry per parameter slot -- and `steps` is the number of timed steps asked for."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '2', '--layers', '2',
+                        '--no-prof', '--no-cpu-baseline', '--no-cold', '--no-secondary', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert res['steps'] == 3 and res['ms_per_step'] > 0 and res['config']['hip_graph']
+    got = {n: np.load(tmp_path / f'{n}.npy') for n in ('loss', 'params', 'grads')}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert float(got['loss'][0]) == res['config']['loss']
+    assert got['params'].size == got['grads'].size == res['config']['params']
+    assert np.isfinite(got['params']).all() and np.isfinite(got['grads']).all() and np.abs(got['grads']).max() > 0
+
+
 @pytest.mark.parametrize('global_batch,per_rank', [(2, 1), (8, 4)])
 def test_bench_gpus_2_strong_scaling_global_batch(global_batch, per_rank):
     """BASELINE.json configs[3] on two ranks: `bench.py --gpus 2 --global-batch B` splits a FIXED global batch over the ranks (one graph

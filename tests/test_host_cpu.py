@@ -675,3 +675,21 @@ def test_topology_parts_of_a_hierarchical_graph():
                                (None, 100, None)):
         t.span = span
         assert t.parts(n_mesh) == want, (span, want)
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per array, whole below the budget; over it, every array keeps the same seeded
+    sample of its elements in index order, the same on every run."""
+    import numpy as np
+    import bench
+    arrays = {'loss': torch.tensor(0.5), 'params': torch.arange(1000, dtype=torch.float32), 'grads': -torch.arange(1000.)}
+    assert bench.dump_outputs(str(tmp_path / 'full'), arrays) == {'loss': (1, 1), 'params': (1000, 1000), 'grads': (1000, 1000)}
+    assert np.array_equal(np.load(tmp_path / 'full' / 'params.npy'), arrays['params'].numpy())
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 2000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 2000
+    assert got['loss'].tolist() == [0.5] and 100 < got['params'].size < 1000
+    assert np.all(np.diff(got['params']) > 0) and np.array_equal(got['grads'], -got['params'])
+    assert all(np.array_equal(got[n], np.load(tmp_path / 'b' / f'{n}.npy')) for n in arrays)
