@@ -125,11 +125,12 @@ class _Agg:
 
 
 class _Latent:
-    __slots__ = ('nodes', 'edges', 'topo', 'splits', 'pre', '_cat')
+    __slots__ = ('nodes', 'edges', 'topo', 'splits', 'pre', 'own', '_cat')
 
     def __init__(self, nodes: List[Tensor], edges: 'OrderedDict[str, Tensor]', topo: Dict[str, topology.EdgeTopology]):
         self.nodes, self.edges, self.topo = nodes, edges, topo
         self.splits = {}
+        self.own = {}       # node part -> the node update's private alias of the rows the block was handed (_enter); taken once
         self.pre = {}       # edge-set name -> (P, zero-filled aggregate buffer) formed by the node kernel of the block before (inference)
         self._cat = None
 
@@ -158,6 +159,20 @@ class _Latent:
         """Two node parts, and every edge set reads one part per side: nobody calls h_all(), so the part tensors are consumed by the
         blocks' own autograd nodes (edge blocks, node updates) only -- what ops.share_grad needs to be vouched for."""
         return len(self.nodes) == 2 and all(t.parts(self.n_mesh) is not None for t in self.topo.values())
+
+
+def _enter(lat: _Latent) -> _Latent:
+    """What a block works on: for every node part it is handed, two private aliases (ops.join) -- `nodes` for the edge blocks, `own`
+    for the part's first node update.  Whoever else holds the caller's tensor (the block before, a skip connection, an auxiliary
+    loss, a forward hook) meets the block's gradient behind the join, as ONE finished tensor; inside, ops.share_grad connects
+    tensors nobody else can hold.  No launch in either direction; without autograd the latent passes through as it is."""
+    if not (torch.is_grad_enabled() and any(h.requires_grad for h in lat.nodes)):
+        return lat
+    pairs = [ops.join(h) if h.requires_grad else (h, h) for h in lat.nodes]
+    out = _Latent([p[1] for p in pairs], lat.edges, lat.topo)
+    out.pre = lat.pre
+    out.own = {i: p[0] for i, p in enumerate(pairs)}
+    return out
 
 
 def _num_rows(node_features) -> int:
@@ -226,7 +241,8 @@ class GraphNet(nn.Module):
         The concatenation is never materialised: every aggregate is its own K-segment of the first Linear -- and an aggregate over
         edges that all arrive in the OTHER part is zero for these rows: its K-segment is left out (ops.fused_mlp: cols)."""
         n_mesh = lat.n_mesh
-        srcs, cols, col = [lat.nodes[which]], [0], lat.nodes[which].shape[1]
+        h = lat.own.pop(which, lat.nodes[which])
+        srcs, cols, col = [h], [0], h.shape[1]
         for a in aggs:
             if a.part is None:
                 # (no slice when there are no hyper rows: its backward would zero-fill and copy a full [N, k*128] gradient)
@@ -237,19 +253,23 @@ class GraphNet(nn.Module):
                 cols.append(col)
             col += a.t.shape[1]
         # (the part's latents are read by this update and by the block's edge blocks -- our own autograd nodes -- only: the update's
-        #  gradient tensor doubles as their accumulation target, ops.share_grad.  One part: the plain blocks; two parts: every
-        #  schedule, as long as no edge set needs the concatenated rows -- torch.cat would be a consumer that reports on its own)
+        #  gradient tensor doubles as their accumulation target, ops.share_grad.  That holds by construction: the rows the block was
+        #  handed are private aliases (_enter), the rows of a later stage were made by this block.  One part: the plain blocks; two
+        #  parts: every schedule, as long as no edge set needs the concatenated rows -- torch.cat would be a consumer that reports
+        #  on its own)
         share = (len(lat.nodes) == 1 and type(self) in (GraphNet, MultiGraphNet, RepeatedGraphNet)) or lat.parts_known()
         lat.nodes[which] = fused_apply(model, srcs, residual=0, cols=cols if len(srcs) <= len(aggs) else None, width=col, share=share)
 
     # -- GraphNet.forward (graphnet.py:72-84) --------------------------------------------------------------------
     def _forward_latent(self, lat: _Latent, nxt: Optional['GraphNet'] = None) -> _Latent:
+        lat = _enter(lat)
         new_edges, aggs = OrderedDict(), OrderedDict()
         for name, feats in lat.edges.items():
             if name not in self.edge_models:
                 raise KeyError(name)                                           # graphnet.py:32
             new_edges[name], aggs[name] = self._edge(lat, feats, name)
         out = _Latent(list(lat.nodes), new_edges, lat.topo)
+        out.own = lat.own
         if nxt is not None:                                                     # (plain blocks only: Processor.forward)
             self._update_nodes(out, aggs, nxt)
         else:
@@ -269,7 +289,7 @@ class GraphNet(nn.Module):
         if post is None:
             self._node(lat, list(aggs.values()), self.node_model_cross, 0)   # graph order (graphnet.py:43)
             return
-        srcs = [lat.nodes[0]] + [a.t for a in aggs.values()]
+        srcs = [lat.own.pop(0, lat.nodes[0])] + [a.t for a in aggs.values()]
         lat.nodes[0], got = fused_apply(self.node_model_cross, srcs, residual=0, post=post, share=len(lat.nodes) == 1)
         if got is not None:
             lat.pre = {next(iter(lat.edges)): got}
@@ -336,7 +356,9 @@ class HyperGraphNet(GraphNet):
 
     def _forward_latent(self, lat):
         src = lat.edges
-        lat = _Latent(list(lat.nodes), src, lat.topo)
+        lat = _enter(lat)
+        lat, own = _Latent(list(lat.nodes), src, lat.topo), lat.own
+        lat.own = own
         new, aggs = OrderedDict(), {}
         E = functools.partial(self._edges_stage, lat, src)
         E('mesh_edges', new, aggs); E('world_edges', new, aggs)

@@ -690,11 +690,17 @@ def share_grad(c: Context, src: torch.Tensor, grad: torch.Tensor) -> None:
     engine would add the two gradients with a pass of its own over [N, 128] (15 launches of 46 us per step of the headline
     model).  The node update's backward runs first (it comes later in the forward): it leaves the gradient tensor it returns for
     `src` here, keyed by the forward tensor's address; an edge block that finds the entry for ITS h accumulates into that tensor
-    (hgn_linear_bwd6a) and returns no gradient of its own.  The engine holds the FIRST gradient it is handed for a tensor by
-    reference until every consumer has reported, so what it passes on is the finished sum -- as long as nobody hands it a second
-    tensor for the same h: it would then add the two into a buffer of its own and the shared tensor would be a dead copy.  Hence:
-    an entry is made only by the first of our functions to report for a tensor, and whoever returns a gradient tensor of its own
-    for a tensor closes its entry for the rest of the run (`unshare_grad`)."""
+    (hgn_linear_bwd6a) and returns no gradient of its own.
+
+    Guarantee: the table only ever connects tensors that nobody outside a block can hold, so a latent may have any other consumer
+    (a skip connection, an auxiliary loss, a forward hook, torch.autograd.grad on it) and still gets the whole sum.  Who vouches:
+    the block (modules._enter), not the caller.  The rows a block is handed pass through `join`, which gives the node update and the
+    edge blocks an alias each; the node update is the only consumer of its alias, so the tensor it returns is that alias's whole
+    gradient, the edge blocks add into it and report nothing for theirs, and the join's backward hands the engine ONE finished
+    tensor for the caller's h -- which the engine adds to whatever else arrived for h, in any order.  Rows made inside a block (the
+    stages of the hierarchical schedules) are consumed by that block's own nodes and by the NEXT block's join only.  An entry is made
+    only by the first of our functions to report for an address; whoever returns a gradient tensor of its own for it, and the join
+    once its sum has left, close it for the rest of the run (`unshare_grad`)."""
     t = _share_table(c)
     if t is None:
         return
@@ -714,6 +720,31 @@ def shared_grad(c: Context, src: torch.Tensor):
     if ent is None or ent[1] != tuple(src.shape) or ent[0].shape != src.shape or not ent[0].is_contiguous():
         return None
     return ent[0]
+
+
+class _JoinFn(torch.autograd.Function):
+    """h -> (alias for the node update, alias for the edge blocks): the two consumers of a node latent inside one block, on tensors
+    of the block's own (share_grad).  No launch forward; backward passes on the node update's tensor, into which the edge blocks
+    have accumulated -- or adds the two when they did not share (sharing off, no packed weights, concatenated node rows)."""
+
+    @staticmethod
+    def forward(ctx, h):
+        ctx.set_materialize_grads(False)
+        ctx.hgn, ctx.key = current(), h.data_ptr()
+        return h.detach(), h.detach()
+
+    @staticmethod
+    def backward(ctx, g_node, g_edge):
+        t = _share_table(ctx.hgn)
+        if t is not None:
+            t[ctx.key] = None            # the sum leaves the block: a later reader of this address reports through the engine
+        if g_edge is None:
+            return g_node
+        return g_edge if g_node is None else g_node + g_edge
+
+
+def join(h: torch.Tensor):
+    return _JoinFn.apply(h)
 
 
 class MLPFn(torch.autograd.Function):
@@ -890,8 +921,8 @@ def fused_mlp(srcs: Sequence[torch.Tensor], w: MLPWeights, idxs: Optional[Sequen
     product, a zero weight gradient.
     `post`: (packs_of(weights of the NEXT edge block), zero-fill wanted) -- the node-level pre-projection of that block (its P = [h W1s^T | h W1r^T]) and the zero fill of its
     aggregate buffer come out of the same launch: -> (out, (P, zeros) or None).
-    `share`: the caller vouches that source 0 (a node latent) is otherwise consumed by EdgeBlockFn nodes only: its gradient tensor is
-    offered to them as their accumulation target (share_grad)."""
+    `share`: the caller vouches that source 0 (a node latent) is otherwise consumed by EdgeBlockFn nodes only -- an alias out of `join`,
+    or rows made inside the block: its gradient tensor is offered to them as their accumulation target (share_grad)."""
     idxs = tuple(idxs) if idxs is not None else (None,) * len(srcs)
     wt = w.tensors()
     train = torch.is_grad_enabled() and any(t.requires_grad for t in list(srcs) + wt)

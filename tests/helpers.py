@@ -316,3 +316,133 @@ class TieMargin:
     def __exit__(self, *exc):
         O.segment_reduce = self._orig
         return False
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The public stage API (encoder / processor blocks / decoder called one at a time on MultiGraphs, meshgraphnet.py:46-51):
+# the same graph and state dict through the HIP classes and through the fp64 oracle's stage functions.
+# ------------------------------------------------------------------------------------------------------------------
+def with_unsorted_receivers(graph, seed=0):
+    """The graph with the rows of every edge set whose receivers come sorted put into a fixed random order, so that the
+    receiver-sort permutation of every set (and its inverse) is not the identity."""
+    gen = torch.Generator().manual_seed(seed)
+    sets = []
+    for e in graph.edge_sets:
+        if e.receivers.numel() > 1 and bool((e.receivers[1:] >= e.receivers[:-1]).all()):
+            p = torch.randperm(e.receivers.numel(), generator=gen)
+            e = e._replace(features=e.features[p], senders=e.senders[p], receivers=e.receivers[p])
+        sets.append(e)
+    return graph._replace(edge_sets=sets)
+
+
+def receivers_unsorted(graph) -> bool:
+    return all(bool((e.receivers[1:] < e.receivers[:-1]).any()) for e in graph.edge_sets)
+
+
+def oracle_params(sd, dtype=torch.float64):
+    return {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in sd.items()}
+
+
+def oracle_graph(node_features, edge_sets, dtype=torch.float64):
+    """Leaf copies (requires_grad) of a graph's features for the oracle; edge_sets: EdgeSets or (name, features, senders, receivers)."""
+    nf = [x.detach().clone().to(dtype).requires_grad_(True) for x in node_features]
+    es = [O.EdgeSet(e[0], e[1].detach().clone().to(dtype).requires_grad_(True), e[2], e[3]) for e in edge_sets]
+    return O.MultiGraph(nf, es)
+
+
+def hip_graph(node_features, edge_sets):
+    """The same on the device, as the package's own MultiGraph."""
+    import hgn_amd
+    nf = [x.detach().clone().cuda().requires_grad_(True) for x in node_features]
+    es = [hgn_amd.EdgeSet(e[0], e[1].detach().clone().cuda().requires_grad_(True), e[2].cuda(), e[3].cuda()) for e in edge_sets]
+    return hgn_amd.MultiGraph(nf, es)
+
+
+def oracle_block(sd, index, graph, arch, agg, set_order=None):
+    """Block `index` of the processor on a public graph (graphnet.py:72-84 and the schedules built on it)."""
+    block = O.BLOCKS.get(arch, (O.graphnet_block, False))[0]
+    bp = f'processor.graphnet_blocks.{index}'
+    if block in (O.hyper_block, O.multiscale_block):
+        return block(sd, bp, graph, agg, set_order)
+    return block(sd, bp, graph, agg)
+
+
+def param_grads(named, like=None):
+    """{name: gradient or zeros} of (name, tensor) pairs."""
+    return {k: (p.grad.detach().clone() if p.grad is not None else torch.zeros_like(p)) for k, p in named}
+
+
+def oracle_staged(sd, graph, arch, agg, steps, target, mask, set_order=None, dtype=torch.float64):
+    """meshgraphnet.py:46-51 stage by stage: -> dict(enc, blocks [public graph after every block], out, loss, grads, in_grads)."""
+    sd = oracle_params(sd, dtype)
+    g0 = oracle_graph(graph.node_features, graph.edge_sets, dtype)
+    enc = O.encoder(sd, g0, O.BLOCKS.get(arch, (None, False))[1])
+    g, blocks = enc, []
+    for i in range(steps):
+        g = oracle_block(sd, i, g, arch, agg, set_order)
+        blocks.append(g)
+    out = O.mlp(sd, 'decoder.model', g.node_features[0], layer_norm=False)
+    loss = O.masked_mse(out, target.to(dtype), mask)
+    loss.backward()
+    return {'enc': enc, 'blocks': blocks, 'out': out.detach(), 'loss': loss.detach(), 'grads': param_grads(sd.items()),
+            'in_grads': {'node': [x.grad for x in g0.node_features], 'edge': {e.name: e.features.grad for e in g0.edge_sets}}}
+
+
+def hip_staged(model, graph, target, mask):
+    """The three stages called in public as the reference's MeshGraphNet.forward calls them, plus every block on its own on the
+    public output of the one before: -> the same dict as oracle_staged, and 'blocks_via_processor' (the processor's own output)."""
+    G = hip_graph(graph.node_features, graph.edge_sets)
+    model.zero_grad(set_to_none=True)
+    enc = model.encoder(G)
+    g, blocks = enc, []
+    for blk in model.processor.graphnet_blocks:
+        g = blk(g)
+        blocks.append(g)
+    latent = model.processor(enc)
+    out = model.decoder(latent._replace(node_features=latent.node_features[0]))
+    loss = torch.nn.functional.mse_loss(target.cuda()[mask.cuda()], out[mask.cuda()])
+    loss.backward()
+    return {'enc': enc, 'blocks': blocks, 'blocks_via_processor': latent, 'out': out.detach(), 'loss': loss.detach(),
+            'grads': param_grads(model.named_parameters()),
+            'in_grads': {'node': [x.grad for x in G.node_features], 'edge': {e.name: e.features.grad for e in G.edge_sets}},
+            'graph': G}
+
+
+class EdgeShare:
+    """Context manager for an fp64 oracle run: the gradient that reaches each node tensor THROUGH the edge updates that read it
+    (graphnet.py:25-29), apart from what the node update and anybody else contribute -- {id(tensor): (tensor, gradient)}."""
+
+    class _Mark(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, rec, key):
+            ctx.rec, ctx.key = rec, key
+            return x.view_as(x)
+
+        @staticmethod
+        def backward(ctx, g):
+            t, acc = ctx.rec[ctx.key]
+            ctx.rec[ctx.key] = (t, g.detach().clone() if acc is None else acc + g.detach())
+            return g, None, None
+
+    def __enter__(self):
+        self.rec = {}
+        self._orig = O.update_edge_features
+
+        def update_edge_features(sd, mlp_prefix, node_features, edge_set):
+            marked = []
+            for x in node_features:
+                if x.requires_grad:
+                    self.rec.setdefault(id(x), (x, None))
+                    x = EdgeShare._Mark.apply(x, self.rec, id(x))
+                marked.append(x)
+            return self._orig(sd, mlp_prefix, marked, edge_set)
+        O.update_edge_features = update_edge_features
+        return self
+
+    def of(self, t):
+        hit = self.rec.get(id(t))
+        return None if hit is None or hit[0] is not t else hit[1]
+
+    def __exit__(self, *exc):
+        O.update_edge_features = self._orig
+        return False
