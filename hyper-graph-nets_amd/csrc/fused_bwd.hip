@@ -656,6 +656,8 @@ static int edge_bwd_fused_impl(const hgn_mlp_bwd_t* a, const hgn_wfuse_t* w, voi
     if (a->n_agg_ops < 1 || a->n_agg_ops > 4 || !a->agg_seg || !a->agg_rowptr || (a->ld_agg & 3) || !aligned16(a->agg_dout))
       return hgn_fail(HGN_E_INVALID, "hgn_edge_bwd_fused: bad aggregation-backward descriptor");
     for (int i = 0; i < a->n_agg_ops; ++i) {
+      if (a->agg_ops[i] == HGN_OP_STD)      // (the struct has no room for data / out / mean)
+        return hgn_fail(HGN_E_INVALID, "hgn_edge_bwd_fused: 'std' (op 4) is not served here: form d_out with hgn_segment_reduce5_bwd / hgn_segment_reduce5_bwd_sorted (base = d_out) first");
       if (a->agg_ops[i] < 0 || a->agg_ops[i] > 3) return hgn_fail(HGN_E_INVALID, "Invalid operation type!");
       if ((a->agg_ops[i] == HGN_OP_MAX && !a->agg_argmax) || (a->agg_ops[i] == HGN_OP_MIN && !a->agg_argmin))
         return hgn_fail(HGN_E_INVALID, "hgn_edge_bwd_fused: max/min need the saved arg index");

@@ -16,7 +16,7 @@ HGN_MAX_WTASK = 16
 PACK_BLOCK_BYTES = 98304
 HGN_MAX_PACK = 32
 NUM_KERNEL_IDS = 15
-OP_CODES = {'sum': 0, 'mean': 1, 'max': 2, 'min': 3}
+OP_CODES = {'sum': 0, 'mean': 1, 'max': 2, 'min': 3, 'std': 4}      # 'std': hgn_segment_reduce5_* only
 F_FP32_MFMA, F_GENERAL_FWD, F_TILE64_FWD, F_DEFER_LN = 1, 2, 4, 8          # hgn_mlp_fwd_t.flags / hgn_mlp_bwd_t.flags / hgn_wtask_t.flags
 KERNEL_NAMES = ['mlp_fwd_edge', 'mlp_fwd', 'mlp_bwd_edge', 'mlp_bwd', 'wgrad', 'seg_fwd', 'seg_bwd', 'linear_fwd',
                 'linear_bwd', 'adam', 'csr', 'wgrad_node', 'seg_fwd_agg', 'features', 'edge_bwd_fused']
@@ -111,6 +111,14 @@ _SIGS = {
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_segment_sum_pair': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_int64, C.c_void_p]),
+    'hgn_segment_reduce5_fwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'hgn_segment_reduce5_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'hgn_segment_reduce5_bwd_sorted': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_segment_std_fwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_void_p]),
     'hgn_segment_std_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,

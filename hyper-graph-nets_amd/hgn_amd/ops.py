@@ -1015,7 +1015,7 @@ class EdgeBlockFn(torch.autograd.Function):
         a.add[1].P = Pr - 4 * ldp * off_r; a.add[1].ld = ldp; a.add[1].idx = topo.rcv.data_ptr()
         saves = _alloc_saves(E, True, dev) if train else None
         _fill_common_fwd(a, w, out, e, saves)
-        agg, amax, amin = None, None, None
+        agg, amax, amin, smean = None, None, None, None
         # `sum` aggregation inside the edge kernel itself (no second pass over e') when the segments are short enough for the
         # in-kernel sums to be order independent (include/hgn_mp.h: seg_out)
         fuse_agg = (agg_ops == ('sum',) and pk is not None and 0 < E and topo.r.max_rows <= _FUSED_SEG_MAX_ROWS
@@ -1034,9 +1034,18 @@ class EdgeBlockFn(torch.autograd.Function):
             if train and 3 in codes:
                 amin = torch.empty(Nr, LAT, dtype=torch.int32, device=dev)
             L.hgn_prof_tag(2)
-            _lib.check(L.hgn_segment_reduce_fwd(out.data_ptr(), LAT, LAT, None, topo.r.rowptr.data_ptr() + 4 * off_r, Nr, arr, k,
-                                                agg.data_ptr(), k * LAT, amax.data_ptr() if amax is not None else None,
-                                                amin.data_ptr() if amin is not None else None, st), 'hgn_segment_reduce_fwd')
+            if OP_CODES['std'] in codes:
+                # 'std' (src/util.py:129-130 through graphnet.py:50-70): the five-operation reduce over e'; the backward needs the mean
+                if train:
+                    smean = torch.empty(Nr, 2 * LAT, device=dev)      # [ mean | what its rounding left over ]: include/hgn_mp.h
+                _lib.check(L.hgn_segment_reduce5_fwd(out.data_ptr(), LAT, LAT, None, topo.r.rowptr.data_ptr() + 4 * off_r, Nr, arr, k,
+                                                     agg.data_ptr(), k * LAT, amax.data_ptr() if amax is not None else None,
+                                                     amin.data_ptr() if amin is not None else None,
+                                                     smean.data_ptr() if smean is not None else None, 2 * LAT, st), 'hgn_segment_reduce5_fwd')
+            else:
+                _lib.check(L.hgn_segment_reduce_fwd(out.data_ptr(), LAT, LAT, None, topo.r.rowptr.data_ptr() + 4 * off_r, Nr, arr, k,
+                                                    agg.data_ptr(), k * LAT, amax.data_ptr() if amax is not None else None,
+                                                    amin.data_ptr() if amin is not None else None, st), 'hgn_segment_reduce_fwd')
             L.hgn_prof_tag(0)
         if train and _GATE_LOG is not None:
             _GATE_LOG.append((wt[0].data_ptr(), saves[4], topo.r.perm))
@@ -1051,13 +1060,17 @@ class EdgeBlockFn(torch.autograd.Function):
             ctx.pk_t = packs_of(w, transposed=True, ctx=c) if pk is not None else None
             ctx.hgn = c
             ctx.rows = (same, off_s, off_r)
-            ctx.save_for_backward(h_s, None if same else h_r, e, *wt)
+            # ('std': the backward differentiates through e' itself, the aggregate and the mean)
+            ctx.n_std = 3 if smean is not None else 0
+            ctx.save_for_backward(h_s, None if same else h_r, e, *wt, *((out, agg, smean) if smean is not None else ()))
         return (out, agg) if agg_ops is not None else out
 
     @staticmethod
     def backward(ctx, d_out, d_agg=None):
         topo = ctx.topo
-        h_s, h_r, e, *wt = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        std_saved = saved[len(saved) - ctx.n_std:] if ctx.n_std else None          # (e', aggregate, mean) of a list with 'std'
+        h_s, h_r, e, *wt = saved[:len(saved) - ctx.n_std]
         same, off_s, off_r = ctx.rows
         if same:
             h_r = h_s
@@ -1082,6 +1095,15 @@ class EdgeBlockFn(torch.autograd.Function):
         if d_out is not None:
             d_out = _rowmajor(d_out)
             b.d_out = d_out.data_ptr(); b.ld_dout = _ld(d_out)
+        g_eff = None
+        if d_agg is not None and std_saved is not None:
+            # 'std' needs e', the aggregate and the mean, for which hgn_mlp_bwd_t has no room: the gradient that reaches e' -- d(e') + the
+            # aggregation backward -- is ALWAYS formed by the streaming pre-pass and handed over as d_out (as for pna below)
+            d_agg = _rowmajor(d_agg)
+            if E > 0:
+                g_eff = _std_prepass(L, st, topo, agg_ops, amax, amin, std_saved, d_agg, d_out, E, Nr, off_r, dev)
+                b.d_out = g_eff.data_ptr(); b.ld_dout = LAT
+            d_agg = None
         if d_agg is not None:
             # d(e') + the aggregation backward are summed inside the kernel's load of d_out (no dE tensor, no extra pass)
             d_agg = _rowmajor(d_agg)
@@ -1230,6 +1252,30 @@ class EdgeBlockFn(torch.autograd.Function):
         return (None, None, None, None, None, dhs[0], dhs[1], de, *grads_w)
 
 
+def _std_prepass(L, st, topo, agg_ops, amax, amin, std_saved, d_agg, d_out, E, Nr, off_r, dev):
+    """-> g_eff [E, 128] = d(e') + the backward of an aggregation whose list contains 'std' (hgn_segment_reduce5_bwd[_sorted])."""
+    e2, agg, smean = std_saved
+    arr, codes = _ops_array(agg_ops)
+    if d_out is not None and (_ld(d_out) != LAT or d_out.data_ptr() % 16):
+        d_out = d_out.contiguous()
+    g_eff = torch.empty(E, LAT, device=dev)
+    ap = amax.data_ptr() if amax is not None else 0
+    an = amin.data_ptr() if amin is not None else 0
+    base = d_out.data_ptr() if d_out is not None else None
+    if E <= 16 * Nr:
+        # rows are in receiver order: one half-wave per receiver loads its gradient, mean and std rows once
+        _lib.check(L.hgn_segment_reduce5_bwd_sorted(d_agg.data_ptr(), _ld(d_agg), topo.r.rowptr.data_ptr() + 4 * off_r, Nr, arr, len(codes),
+                                                    ap or None, an or None, base, g_eff.data_ptr(), LAT, e2.data_ptr(), LAT,
+                                                    agg.data_ptr(), _ld(agg), smean.data_ptr(), 2 * LAT, st), 'hgn_segment_reduce5_bwd_sorted')
+    else:       # few long segments (the rows that arrive at a hyper node): a half-wave per ROW; per-receiver arrays by global row number
+        _lib.check(L.hgn_segment_reduce5_bwd(d_agg.data_ptr() - 4 * _ld(d_agg) * off_r, _ld(d_agg), LAT, None, topo.rcv.data_ptr(),
+                                             topo.r.rowptr.data_ptr(), E, arr, len(codes),
+                                             ap - 4 * LAT * off_r if ap else None, an - 4 * LAT * off_r if an else None,
+                                             base, g_eff.data_ptr(), LAT, e2.data_ptr(), LAT, agg.data_ptr() - 4 * _ld(agg) * off_r, _ld(agg),
+                                             smean.data_ptr() - 4 * 2 * LAT * off_r, 2 * LAT, st), 'hgn_segment_reduce5_bwd')
+    return g_eff
+
+
 def edge_block(h_all: torch.Tensor, e_sorted: torch.Tensor, topo, w: MLPWeights, agg_ops=None, pre=None, parts=None, h_r=None):
     """-> e'   or, with ``agg_ops`` (e.g. ('sum',) or the four PNA ops),  (e', agg[N, len(ops)*128]).
     ``parts = (off_s, off_r)`` [+ ``h_r``]: node rows by part (EdgeBlockFn); the aggregate then has the receiver part's rows only."""
@@ -1253,7 +1299,8 @@ def _ops_array(ops: Sequence[str]):
 
 
 class AggregateFn(torch.autograd.Function):
-    """[N, n_sets * n_ops * D]: per edge set (sorted layout, perm=None, or user layout with its CSR perm), per op."""
+    """[N, n_sets * n_ops * D]: per edge set (sorted layout, perm=None, or user layout with its CSR perm), per op.  `ops` may hold 'std'
+    in any slot (hgn_segment_reduce5_*): the backward then reads the rows, the aggregate and the per-set means again."""
 
     @staticmethod
     def forward(ctx, csrs, ops, train, *datas):
@@ -1267,19 +1314,32 @@ class AggregateFn(torch.autograd.Function):
         k = len(codes)
         width = len(datas) * k * D
         out = torch.empty(N, width, device=dev)
-        need_arg = train and any(c >= 2 for c in codes)
-        args = []
+        need_arg = train and any(c in (2, 3) for c in codes)
+        has_std = OP_CODES['std'] in codes
+        args, means = [], []
         for i, (d, (perm, rowptr, seg)) in enumerate(zip(datas, csrs)):
             amax = torch.empty(N, D, dtype=torch.int32, device=dev) if need_arg and 2 in codes else None
             amin = torch.empty(N, D, dtype=torch.int32, device=dev) if need_arg and 3 in codes else None
-            _lib.check(L.hgn_segment_reduce_fwd(d.data_ptr(), _ld(d), D, perm.data_ptr() if perm is not None else None,
-                                                rowptr.data_ptr(), N, arr, k, out.data_ptr() + 4 * i * k * D, width,
-                                                amax.data_ptr() if amax is not None else None,
-                                                amin.data_ptr() if amin is not None else None, _lib.stream_ptr()),
-                       'hgn_segment_reduce_fwd')
+            if has_std:
+                mean = torch.empty(N, 2 * D, device=dev) if train else None      # [ mean | what its rounding left over ]
+                _lib.check(L.hgn_segment_reduce5_fwd(d.data_ptr(), _ld(d), D, perm.data_ptr() if perm is not None else None,
+                                                     rowptr.data_ptr(), N, arr, k, out.data_ptr() + 4 * i * k * D, width,
+                                                     amax.data_ptr() if amax is not None else None,
+                                                     amin.data_ptr() if amin is not None else None,
+                                                     mean.data_ptr() if mean is not None else None, 2 * D, _lib.stream_ptr()),
+                           'hgn_segment_reduce5_fwd')
+                means.append(mean)
+            else:
+                _lib.check(L.hgn_segment_reduce_fwd(d.data_ptr(), _ld(d), D, perm.data_ptr() if perm is not None else None,
+                                                    rowptr.data_ptr(), N, arr, k, out.data_ptr() + 4 * i * k * D, width,
+                                                    amax.data_ptr() if amax is not None else None,
+                                                    amin.data_ptr() if amin is not None else None, _lib.stream_ptr()),
+                           'hgn_segment_reduce_fwd')
             args.append((amax, amin))
         if train:
             ctx.cfg = (csrs, ops, [tuple(d.shape) for d in datas], args, width)
+            if has_std:
+                ctx.save_for_backward(out, *datas, *means)
         return out
 
     @staticmethod
@@ -1290,6 +1350,10 @@ class AggregateFn(torch.autograd.Function):
         k = len(codes)
         d_out = _rowmajor(d_out)
         dev = d_out.device
+        has_std = OP_CODES['std'] in codes
+        if has_std:
+            out, *rest = ctx.saved_tensors
+            datas, means = rest[:len(shapes)], rest[len(shapes):]
         grads = []
         for i, ((perm, rowptr, seg), shp, (amax, amin)) in enumerate(zip(csrs, shapes, args)):
             if not ctx.needs_input_grad[3 + i]:
@@ -1297,12 +1361,21 @@ class AggregateFn(torch.autograd.Function):
                 continue
             E, D = shp
             g = torch.empty(E, D, device=dev)
-            _lib.check(L.hgn_segment_reduce_bwd(d_out.data_ptr() + 4 * i * k * D, _ld(d_out), D,
-                                                perm.data_ptr() if perm is not None else None, seg.data_ptr(),
-                                                rowptr.data_ptr(), E, arr, k,
-                                                amax.data_ptr() if amax is not None else None,
-                                                amin.data_ptr() if amin is not None else None, None, g.data_ptr(), D,
-                                                _lib.stream_ptr()), 'hgn_segment_reduce_bwd')
+            if has_std:
+                _lib.check(L.hgn_segment_reduce5_bwd(d_out.data_ptr() + 4 * i * k * D, _ld(d_out), D,
+                                                     perm.data_ptr() if perm is not None else None, seg.data_ptr(),
+                                                     rowptr.data_ptr(), E, arr, k,
+                                                     amax.data_ptr() if amax is not None else None,
+                                                     amin.data_ptr() if amin is not None else None, None, g.data_ptr(), D,
+                                                     datas[i].data_ptr(), _ld(datas[i]), out.data_ptr() + 4 * i * k * D, width,
+                                                     means[i].data_ptr(), 2 * D, _lib.stream_ptr()), 'hgn_segment_reduce5_bwd')
+            else:
+                _lib.check(L.hgn_segment_reduce_bwd(d_out.data_ptr() + 4 * i * k * D, _ld(d_out), D,
+                                                    perm.data_ptr() if perm is not None else None, seg.data_ptr(),
+                                                    rowptr.data_ptr(), E, arr, k,
+                                                    amax.data_ptr() if amax is not None else None,
+                                                    amin.data_ptr() if amin is not None else None, None, g.data_ptr(), D,
+                                                    _lib.stream_ptr()), 'hgn_segment_reduce_bwd')
             grads.append(g)
         return (None, None, None, *grads)
 

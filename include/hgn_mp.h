@@ -37,6 +37,7 @@ extern "C" {
 #define HGN_OP_MEAN 1
 #define HGN_OP_MAX 2
 #define HGN_OP_MIN 3
+#define HGN_OP_STD 4   /* hgn_segment_reduce5_* only: every other entry that takes op codes refuses it and names those */
 #define HGN_F_FP32_MFMA 1
 #define HGN_F_GENERAL_FWD 2
 #define HGN_F_TILE64_FWD 4   /* A/B switch: 64-row forward tiles (three workgroups per CU) also for launches that would take 128-row tiles */
@@ -108,11 +109,39 @@ int hgn_segment_reduce_bwd_sorted(const float* d_out, int64_t ld_out, const int3
 int hgn_segment_sum_pair(const float* data, int64_t ld, const int32_t* rowptr_a, const int32_t* perm_b, const int32_t* rowptr_b, int64_t N,
                          float* out_a, int64_t ld_a, float* out_b, int64_t ld_b, void* stream);
 /* The fifth operation of util.unsorted_segment_operation, 'std' (src/util.py:129-130 -> torch_scatter.scatter_std with its default
- * unbiased = True; unreachable from the reference's configs).  torch-scatter 2.0.9 (torch_scatter/composite/std.py) as published:
+ * unbiased = True).  None of the YAMLs the reference ships asks for it, but the config key does reach it: GraphNet.aggregation
+ * (graphnet.py:50-70) hands every aggregator string other than 'pna' to util.unsorted_segment_operation, so `aggregation: std`, or the
+ * string given to MeshGraphNet(...) / a GraphNet block, trains a model there.  torch-scatter 2.0.9 (torch_scatter/composite/std.py) as
+ * published:
  *   count = max(#rows of the segment, 1);  mean = sum / count;  out = sqrt( sum (x - mean)^2 / (max(count - 1, 1) + 1e-6) )
- * so an empty segment gives 0.  `mean` (nullable, [N, ld_out]) is written for the backward pass, which is the autograd of that
- * composite:  d_data[pos][d] = d_out[n][d] (x - mean[n][d]) / (out[n][d] (max(count - 1, 1) + 1e-6))  -- NaN (0 / 0) for the rows of a
- * segment without variance, exactly like the wheel's sqrt'(0) * 0. */
+ * so an empty segment gives 0.  Two sweeps over the segment's rows (mean, then squared deviations), never sum and sum of squares.
+ * `mean` (nullable) is written for the backward pass, which is the autograd of that composite:
+ *   d_data[pos][d] += d_out[n][slot*D + d] (x - mean[n][d]) / (out[n][slot*D + d] (max(count - 1, 1) + 1e-6))
+ * hgn_segment_std_fwd / _bwd: mean is [N, ld_out].  hgn_segment_reduce5_*: mean is [N, ld_mean >= 2 D], the mean in TWO fp32 words
+ * [ mean | res ], res = sum (x - mean) / count (what the rounding of the mean left over), and the backward evaluates (x - mean) - res:
+ * the composite's autograd routes -sum d(dev) / count through the mean, so a segment's gradient rows sum to zero whatever that rounding
+ * was, and the column sums over all edge rows that form an edge model's bias gradients depend on it (1e-3 at 15 layers without).
+ * -- NaN (0 / 0) for the rows of a segment WITHOUT VARIANCE (one row, or all rows equal), exactly like the wheel's sqrt'(0) * 0 and
+ * the reference.  That is kept on purpose.
+ *
+ * hgn_segment_reduce5_*: hgn_segment_reduce_fwd / _bwd / _bwd_sorted for op lists that may hold HGN_OP_STD in any slot, beside sum / mean /
+ * max / min, in the same pass (graphnet.py:50-70 + src/util.py:116-130); the hot path of a model with `message_passing_aggregator='std'`.
+ * Same layout and rules as those entries; a list without 'std' is passed on to them unchanged, and the sum / mean / max / min slots
+ * of a mixed list are bit-identical to theirs.  The backward forms need the reduced rows `data` (row pos = perm ? perm[j] : j), the
+ * forward's output `out` ([N, ld_fwd], slot layout of the forward) and `mean` ([N, ld_mean >= 2 D]): null for a list with 'std' -> HGN_E_INVALID.  The two
+ * backward forms agree bit for bit.  D = 128 with 16-byte aligned rows: half a wavefront x float4 per row; any other D: thread per element. */
+int hgn_segment_reduce5_fwd(const float* data, int64_t ld_data, int D, const int32_t* perm, const int32_t* rowptr, int64_t num_segments,
+                            const int32_t* ops /*host*/, int n_ops, float* out, int64_t ld_out, int32_t* argmax, int32_t* argmin,
+                            float* mean, int64_t ld_mean, void* stream);
+int hgn_segment_reduce5_bwd(const float* d_out, int64_t ld_out, int D, const int32_t* perm, const int32_t* seg, const int32_t* rowptr,
+                            int64_t num_edges, const int32_t* ops /*host*/, int n_ops, const int32_t* argmax, const int32_t* argmin,
+                            const float* base, float* d_data, int64_t ld_d, const float* data, int64_t ld_data, const float* out,
+                            int64_t ld_fwd, const float* mean, int64_t ld_mean, void* stream);
+int hgn_segment_reduce5_bwd_sorted(const float* d_out, int64_t ld_out, const int32_t* rowptr, int64_t N, const int32_t* ops /*host*/, int n_ops,
+                                   const int32_t* argmax, const int32_t* argmin, const float* base, float* d_data, int64_t ld_d,
+                                   const float* data, int64_t ld_data, const float* out, int64_t ld_fwd, const float* mean, int64_t ld_mean,
+                                   void* stream);
+/* The stand-alone form of 'std' alone (util.unsorted_segment_operation(..., 'std') called directly): thread per (segment, column). */
 int hgn_segment_std_fwd(const float* data, int64_t ld_data, int D, const int32_t* perm, const int32_t* rowptr, int64_t N,
                         float* out, int64_t ld_out, float* mean, void* stream);
 int hgn_segment_std_bwd(const float* d_out, const float* out, const float* mean, int64_t ld_out, const float* data,
