@@ -315,6 +315,156 @@ __global__ void forman_post_delta_kernel(const float* __restrict__ A, const floa
   if (lane == 0) D[p] = forman_value(dmax, dmin, a2xy, axy, cnt, mx);
 }
 
+// ----------------------------------------------------------------------------------------------------------
+// backward of the feature kernels (the statistics of the normaliser are constants: nothing flows into them)
+// ----------------------------------------------------------------------------------------------------------
+// Relative-position features.  With u = a[s]-a[r] the gradient of u is g = d_feat[0:da] + (d_feat[da] + d_len) * u/|u|
+// (the norm term is dropped where |u| = 0); node s receives +g, node r receives -g.  Parallel over NODES: a node walks
+// its outgoing edges (CSR by sender), then its incoming ones (CSR by receiver), in CSR order, and writes its row once:
+// no atomics, the same bits on every run.  Per edge it reads the edge id, the other end's id and row and 8-32 bytes
+// of d_feat -- gathered, so the pass is bound by memory latency: a thread per node while a node has few edges (a mesh
+// node has ~12), a wavefront per node above REL_BWD_WAVE_DEG (lanes stride over the edge list, xor-butterfly sum).
+constexpr int REL_BWD_WAVE_DEG = 32;
+
+struct RelBwd {
+  const float *a, *b, *d_feat, *d_len;
+  long lda, ldb, ldf;
+  int da, db;
+  long n_rows, E;
+  const int64_t *snd, *rcv;
+  const int *rp_s, *perm_s, *rp_r, *perm_r;
+  float *d_a, *d_b;
+};
+
+__device__ __forceinline__ int clamp_ptr(int v, long E) { return v < 0 ? 0 : (v > E ? (int)E : v); }
+
+// position k of the sender (out = true) or receiver CSR of node n: adds the edge's share to ga / gb
+__device__ __forceinline__ void rel_bwd_edge(const RelBwd& p, const float* an, const float* bn, int k, bool out, float* ga,
+                                             float* gb) {
+  const long e = out ? p.perm_s[k] : p.perm_r[k];
+  if (e < 0 || e >= p.E) return;
+  const int64_t o = out ? p.rcv[e] : p.snd[e];
+  if (o < 0 || o >= p.n_rows) return;
+  const float sg = out ? 1.f : -1.f;
+  const float* df = p.d_feat ? p.d_feat + e * p.ldf : nullptr;
+  if (p.d_a) {
+    float u[3], q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float ao = i < p.da ? p.a[o * p.lda + i] : 0.f;
+      u[i] = i < p.da ? (out ? an[i] - ao : ao - an[i]) : 0.f;      // a[s] - a[r], as the forward forms it
+      q += u[i] * u[i];
+    }
+    const float c = (df ? df[p.da] : 0.f) + (p.d_len ? p.d_len[e] : 0.f);
+    const float nrm = sqrtf(q);
+    const float w = nrm > 0.f ? c / nrm : 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      if (i < p.da) ga[i] += sg * ((df ? df[i] : 0.f) + w * u[i]);
+  }
+  if (p.d_b && df) {
+    const float* dg = df + p.da + 1;
+    float u[3], q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float bo = i < p.db ? p.b[o * p.ldb + i] : 0.f;
+      u[i] = i < p.db ? (out ? bn[i] - bo : bo - bn[i]) : 0.f;
+      q += u[i] * u[i];
+    }
+    const float nrm = sqrtf(q);
+    const float w = nrm > 0.f ? dg[p.db] / nrm : 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      if (i < p.db) gb[i] += sg * (dg[i] + w * u[i]);
+  }
+}
+
+__device__ __forceinline__ void rel_bwd_own_rows(const RelBwd& p, long n, float* an, float* bn) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    an[i] = (p.d_a && i < p.da) ? p.a[n * p.lda + i] : 0.f;
+    bn[i] = (p.d_b && i < p.db) ? p.b[n * p.ldb + i] : 0.f;
+  }
+}
+
+// split != 0: rows of more than REL_BWD_WAVE_DEG edges are left to rel_edge_bwd_wave_kernel
+__global__ void rel_edge_bwd_thread_kernel(RelBwd p, int split) {
+  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= p.n_rows) return;
+  const int s0 = clamp_ptr(p.rp_s[n], p.E), s1 = clamp_ptr(p.rp_s[n + 1], p.E);
+  const int r0 = clamp_ptr(p.rp_r[n], p.E), r1 = clamp_ptr(p.rp_r[n + 1], p.E);
+  if (split && (long)(s1 - s0) + (r1 - r0) > REL_BWD_WAVE_DEG) return;
+  float an[3], bn[3], ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
+  rel_bwd_own_rows(p, n, an, bn);
+  for (int k = s0; k < s1; ++k) rel_bwd_edge(p, an, bn, k, true, ga, gb);
+  for (int k = r0; k < r1; ++k) rel_bwd_edge(p, an, bn, k, false, ga, gb);
+  if (p.d_a)
+    for (int i = 0; i < p.da; ++i) p.d_a[n * p.da + i] = ga[i];
+  if (p.d_b)
+    for (int i = 0; i < p.db; ++i) p.d_b[n * p.db + i] = gb[i];
+}
+
+// one wavefront per row of more than REL_BWD_WAVE_DEG edges (the other rows belong to the thread kernel)
+__global__ void rel_edge_bwd_wave_kernel(RelBwd p) {
+  const int lane = threadIdx.x & 63;
+  const long n = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= p.n_rows) return;
+  const int s0 = clamp_ptr(p.rp_s[n], p.E), s1 = clamp_ptr(p.rp_s[n + 1], p.E);
+  const int r0 = clamp_ptr(p.rp_r[n], p.E), r1 = clamp_ptr(p.rp_r[n + 1], p.E);
+  const long n_out = s1 > s0 ? s1 - s0 : 0, n_in = r1 > r0 ? r1 - r0 : 0;
+  if (n_out + n_in <= REL_BWD_WAVE_DEG) return;                  // uniform per wave
+  float an[3], bn[3], ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
+  rel_bwd_own_rows(p, n, an, bn);
+  for (long j = lane; j < n_out + n_in; j += 64) {               // outgoing edges first, then incoming, lane-strided
+    if (j < n_out) rel_bwd_edge(p, an, bn, s0 + (int)j, true, ga, gb);
+    else rel_bwd_edge(p, an, bn, r0 + (int)(j - n_out), false, ga, gb);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1)                              // fixed pairing: deterministic
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      ga[i] += __shfl_xor(ga[i], o);
+      gb[i] += __shfl_xor(gb[i], o);
+    }
+  if (lane == 0) {
+    if (p.d_a)
+      for (int i = 0; i < p.da; ++i) p.d_a[n * p.da + i] = ga[i];
+    if (p.d_b)
+      for (int i = 0; i < p.db; ++i) p.d_b[n * p.db + i] = gb[i];
+  }
+}
+
+// node features: the velocity columns pass +d to cur and -d to prev (zero on rows the forward masked); flat over [N, d]
+__global__ void node_feat_bwd_kernel(const float* __restrict__ d_out, long ldo, int d, int n_classes, int vel_first,
+                                     const int64_t* __restrict__ node_type, long ldt, int vel_mask_type, long N,
+                                     float* __restrict__ d_cur, float* __restrict__ d_prev) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * d) return;
+  const long n = i / d;
+  const int c = (int)(i - n * d);
+  float g = d_out[n * ldo + (vel_first ? c : c + n_classes)];
+  if (vel_mask_type >= 0 && node_type[n * ldt] != vel_mask_type) g = 0.f;
+  if (d_cur) d_cur[i] = g;
+  if (d_prev) d_prev[i] = -g;
+}
+
+__global__ void normalize_bwd_kernel(const float* __restrict__ d_out, long n_elem, int F, const float* __restrict__ acc_sum,
+                                     const float* __restrict__ acc_sumsq, const float* __restrict__ acc_count, float eps,
+                                     int inverse, float* __restrict__ d_x) {
+  __shared__ float sd[HGN_MAX_FEATURE_WIDTH];
+  if ((int)threadIdx.x < F) {                                   // the std of normalize_kernel, op for op
+    const float safe = fmaxf(*acc_count, 1.f);
+    const float m = acc_sum[threadIdx.x] / safe;
+    const float s = sqrtf(fabsf(acc_sumsq[threadIdx.x] / safe - m * m));
+    sd[threadIdx.x] = fmaxf(s, eps);
+  }
+  __syncthreads();
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_elem) return;
+  const int c = (int)(i % F);
+  d_x[i] = inverse ? d_out[i] * sd[c] : d_out[i] / sd[c];
+}
+
 static int stats_blocks(int64_t rows, int F, int* active) {
   *active = (ST / F) * F;
   const int64_t n = rows * F;
@@ -558,4 +708,69 @@ extern "C" int hgn_forman_post_delta(const float* A, const float* A2, float d_in
   hipLaunchKernelGGL(forman_post_delta_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, stream, A, A2, d_in_x, d_out_y,
                      (long)N, x, y, i_nb, dim_i, j_nb, dim_j, D);
   return hgn_check_launch("hgn_forman_post_delta");
+}
+
+extern "C" int hgn_rel_edge_features_bwd(const float* d_feat, int64_t ldf, const float* d_len, const float* a, int64_t lda,
+                                         int da, const float* b, int64_t ldb, int db, int64_t n_rows,
+                                         const int64_t* senders, const int64_t* receivers, int64_t E,
+                                         const int32_t* rowptr_s, const int32_t* perm_s, const int32_t* rowptr_r,
+                                         const int32_t* perm_r, int64_t max_degree, float* d_a, float* d_b, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (E < 0 || E > 0x7fffffffLL || n_rows < 0 || da < 1 || da > 3 || db < 0 || db > 3 || lda < da || (db > 0 && ldb < db))
+    return hgn_fail(HGN_E_INVALID, "hgn_rel_edge_features_bwd: sizes must satisfy 1<=da<=3, 0<=db<=3, ld >= width, E < 2^31");
+  const int W = da + 1 + (db > 0 ? db + 1 : 0);
+  if (d_feat && ldf < W) return hgn_fail(HGN_E_INVALID, "hgn_rel_edge_features_bwd: ldf smaller than the feature row");
+  if (d_b && db == 0) return hgn_fail(HGN_E_INVALID, "hgn_rel_edge_features_bwd: d_b given with db = 0");
+  if (n_rows == 0 || (!d_a && !d_b)) return HGN_OK;
+  if (E == 0 || (!d_feat && !d_len)) {                 // no edge, or no gradient arriving: every row is zero
+    if ((d_a && hipMemsetAsync(d_a, 0, (size_t)n_rows * da * sizeof(float), stream) != hipSuccess) ||
+        (d_b && hipMemsetAsync(d_b, 0, (size_t)n_rows * db * sizeof(float), stream) != hipSuccess))
+      return hgn_check_launch("hgn_rel_edge_features_bwd memset");
+    return HGN_OK;
+  }
+  if (!a || (d_b && !b) || !senders || !receivers || !rowptr_s || !perm_s || !rowptr_r || !perm_r)
+    return hgn_fail(HGN_E_INVALID, "hgn_rel_edge_features_bwd: null pointer");
+  ProfScope ps(13, (double)E, stream);
+  RelBwd p;
+  p.a = a; p.b = b; p.d_feat = d_feat; p.d_len = d_len;
+  p.lda = (long)lda; p.ldb = (long)ldb; p.ldf = (long)ldf;
+  p.da = da; p.db = db; p.n_rows = (long)n_rows; p.E = (long)E;
+  p.snd = senders; p.rcv = receivers;
+  p.rp_s = rowptr_s; p.perm_s = perm_s; p.rp_r = rowptr_r; p.perm_r = perm_r;
+  p.d_a = d_a; p.d_b = d_b;
+  const int split = (max_degree < 0 || max_degree > REL_BWD_WAVE_DEG) ? 1 : 0;
+  hipLaunchKernelGGL(rel_edge_bwd_thread_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, stream, p, split);
+  if (split)
+    hipLaunchKernelGGL(rel_edge_bwd_wave_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, stream, p);
+  return hgn_check_launch("hgn_rel_edge_features_bwd");
+}
+
+extern "C" int hgn_node_features_bwd(const float* d_out, int64_t ldo, int d, int n_classes, int vel_first,
+                                     const int64_t* node_type, int64_t ldt, int vel_mask_type, int64_t N, float* d_cur,
+                                     float* d_prev, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N < 0 || d < 0 || n_classes < 0 || d + n_classes < 1 || d + n_classes > HGN_MAX_FEATURE_WIDTH || ldo < d + n_classes ||
+      ldt < 1)
+    return hgn_fail(HGN_E_INVALID, "hgn_node_features_bwd: bad widths / strides");
+  if (N == 0 || d == 0 || (!d_cur && !d_prev)) return HGN_OK;
+  if (!d_out || (vel_mask_type >= 0 && !node_type)) return hgn_fail(HGN_E_INVALID, "hgn_node_features_bwd: null pointer");
+  ProfScope ps(13, (double)N, stream);
+  const int64_t n = N * d;
+  hipLaunchKernelGGL(node_feat_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, (long)ldo, d,
+                     n_classes, vel_first, node_type, (long)ldt, vel_mask_type, (long)N, d_cur, d_prev);
+  return hgn_check_launch("hgn_node_features_bwd");
+}
+
+extern "C" int hgn_normalize_bwd(const float* d_out, int64_t rows, int F, const float* acc_sum, const float* acc_sumsq,
+                                 const float* acc_count, float eps, int inverse, float* d_x, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (rows < 0 || F < 1 || F > HGN_MAX_FEATURE_WIDTH || !acc_sum || !acc_sumsq || !acc_count)
+    return hgn_fail(HGN_E_INVALID, "hgn_normalize_bwd: null pointer or bad width");
+  if (rows == 0) return HGN_OK;
+  if (!d_out || !d_x) return hgn_fail(HGN_E_INVALID, "hgn_normalize_bwd: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  const int64_t n = rows * F;
+  hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, (long)n, F, acc_sum,
+                     acc_sumsq, acc_count, eps, inverse, d_x);
+  return hgn_check_launch("hgn_normalize_bwd");
 }

@@ -186,6 +186,14 @@ _SIGS = {
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'hgn_lincomb3': (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_int64,
                                C.c_void_p, C.c_void_p]),
+    'hgn_rel_edge_features_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                            C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    'hgn_node_features_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hgn_normalize_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                    C.c_int, C.c_void_p, C.c_void_p]),
     'hgn_prof_enable': (C.c_int, [C.c_int]),
     'hgn_prof_tag': (C.c_int, [C.c_int]),
     'hgn_prof_reset': (C.c_int, []),

@@ -5,7 +5,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, topology
 from .ops import _workspace
 
 
@@ -51,10 +51,88 @@ def cells_to_edges(cells: torch.Tensor, deform: bool = False):
     return s[:2 * n.value], r[:2 * n.value], n.value
 
 
+def _needs_grad(*tensors) -> bool:
+    """Whether a call has to become an autograd node: grad mode on and a floating input that requires grad.  Otherwise the
+    wrappers below launch exactly what they launched before they could be differentiated."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad for t in tensors)
+
+
+def _like(grad, ref: torch.Tensor):
+    """A gradient in the shape, dtype and place of the input it belongs to."""
+    return None if grad is None else grad.reshape(ref.shape).to(device=ref.device, dtype=ref.dtype)
+
+
+def rel_edge_features_bwd(d_feat, d_len, a: torch.Tensor, b, senders: torch.Tensor, receivers: torch.Tensor,
+                          want_a: bool = True, want_b: bool = True):
+    """Gradient of rel_edge_features with respect to ``a`` / ``b`` (hgn_rel_edge_features_bwd): node-parallel over the CSRs of
+    the edges by sender and by receiver (topology.segment_csr: cached on the id tensors), no atomics, deterministic.
+    ``d_feat`` [E, W] and ``d_len`` [E] may each be None.  -> (d_a or None, d_b or None)."""
+    _lib.require_gpu(a)
+    dev = a.device
+    a = _f32_rows(a)
+    N, da = a.shape
+    db = 0
+    if b is not None:
+        b = _f32_rows(b.to(dev))
+        db = b.shape[1]
+        if b.shape[0] != N:
+            raise ValueError('a and b must have the same number of rows')
+    want_b = want_b and db > 0
+    s, r = _ids(senders, dev), _ids(receivers, dev)
+    E = s.shape[0]
+    if r.shape[0] != E:
+        raise ValueError('senders / receivers length mismatch')
+    W = da + 1 + (db + 1 if db else 0)
+    if d_feat is not None:
+        d_feat = _f32_rows(d_feat.to(dev))
+        if tuple(d_feat.shape) != (E, W):
+            raise ValueError(f'd_feat must be [{E}, {W}]')
+    if d_len is not None:
+        d_len = d_len.to(dev).float().reshape(-1).contiguous()
+        if d_len.shape[0] != E:
+            raise ValueError(f'd_len must be [{E}]')
+    d_a = torch.empty(N, da, dtype=torch.float32, device=dev) if want_a else None
+    d_b = torch.empty(N, db, dtype=torch.float32, device=dev) if want_b else None
+    cs = cr = None
+    if E > 0:
+        cs, cr = topology.segment_csr(s, N, dev), topology.segment_csr(r, N, dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.check(_lib.lib().hgn_rel_edge_features_bwd(
+        ptr(d_feat), _ld(d_feat) if d_feat is not None else 0, ptr(d_len), a.data_ptr(), _ld(a), da,
+        b.data_ptr() if db else None, _ld(b) if db else 0, db, N, s.data_ptr(), r.data_ptr(), E,
+        ptr(cs.rowptr) if cs else None, ptr(cs.perm) if cs else None, ptr(cr.rowptr) if cr else None,
+        ptr(cr.perm) if cr else None, cs.max_rows + cr.max_rows if cs else 0, ptr(d_a), ptr(d_b), _lib.stream_ptr()),
+        'hgn_rel_edge_features_bwd')
+    return d_a, d_b
+
+
+class _RelEdgeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, senders, receivers, want_feat, want_len):
+        ctx.set_materialize_grads(False)
+        feat, ln = rel_edge_features(a.detach(), b.detach() if b is not None else None, senders, receivers, want_feat, want_len)
+        ctx.ids = (senders, receivers)
+        ctx.has_b = b is not None
+        ctx.save_for_backward(a, *([b] if b is not None else []))
+        return feat, ln
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_feat, d_len):
+        a = ctx.saved_tensors[0]
+        b = ctx.saved_tensors[1] if ctx.has_b else None
+        want_a, want_b = ctx.needs_input_grad[0], ctx.has_b and ctx.needs_input_grad[1]
+        d_a, d_b = rel_edge_features_bwd(d_feat, d_len, a, b, *ctx.ids, want_a=want_a, want_b=want_b)
+        return _like(d_a, a), (_like(d_b, b) if d_b is not None else None), None, None, None, None
+
+
 def rel_edge_features(a: torch.Tensor, b, senders: torch.Tensor, receivers: torch.Tensor, want_feat: bool = True,
                       want_len: bool = False):
-    """[a[s]-a[r], |.|, b[s]-b[r], |.|] per edge (b may be None) and/or the length |a[s]-a[r]|."""
+    """[a[s]-a[r], |.|, b[s]-b[r], |.|] per edge (b may be None) and/or the length |a[s]-a[r]|.  Differentiable with
+    respect to ``a`` and ``b``."""
     _lib.require_gpu(a)
+    if _needs_grad(a, b):
+        return _RelEdgeFn.apply(a, b, senders, receivers, want_feat, want_len)
     dev = a.device
     a = _f32_rows(a)
     da = a.shape[1]
@@ -92,11 +170,43 @@ def _class_map(mapping, dev):
     return t
 
 
+class _NodeFeaturesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cur, prev, node_type, mapping, n_classes, vel_first, vel_mask_type, d):
+        out = node_features(cur.detach() if cur is not None else None, prev.detach() if prev is not None else None, node_type,
+                            mapping, n_classes, vel_first, vel_mask_type, d)
+        ctx.cfg = (node_type, n_classes, vel_first, vel_mask_type, cur, prev)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        node_type, n_classes, vel_first, vel_mask_type, cur, prev = ctx.cfg
+        dev = d_out.device
+        d_out = _f32_rows(d_out)
+        N = d_out.shape[0]
+        d = d_out.shape[1] - n_classes
+        nt = node_type.to(device=dev, dtype=torch.int64)
+        if nt.dim() == 2:
+            nt = nt[:, 0]
+        ldt = nt.stride(0) if N > 1 else 1
+        d_cur = torch.empty(N, d, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        d_prev = torch.empty(N, d, dtype=torch.float32, device=dev) if prev is not None and ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().hgn_node_features_bwd(
+            d_out.data_ptr(), _ld(d_out), d, n_classes, 1 if vel_first else 0, nt.data_ptr(), ldt, vel_mask_type, N,
+            d_cur.data_ptr() if d_cur is not None else None, d_prev.data_ptr() if d_prev is not None else None,
+            _lib.stream_ptr()), 'hgn_node_features_bwd')
+        return (_like(d_cur, cur) if d_cur is not None else None, _like(d_prev, prev) if d_prev is not None else None,
+                None, None, None, None, None, None)
+
+
 def node_features(cur, prev, node_type: torch.Tensor, mapping, n_classes: int, vel_first: bool = True,
                   vel_mask_type: int = -1, d: int = None) -> torch.Tensor:
     """[velocity | one-hot(class)] (or [one-hot | velocity]); ``node_type`` is the reference's [N, 1] (or [N]) tensor,
-    ``mapping`` an optional tuple raw type -> class."""
+    ``mapping`` an optional tuple raw type -> class.  Differentiable with respect to ``cur`` and ``prev``."""
     _lib.require_gpu(node_type)
+    if _needs_grad(cur, prev):
+        return _NodeFeaturesFn.apply(cur, prev, node_type, mapping, n_classes, vel_first, vel_mask_type, d)
     dev = node_type.device
     nt = node_type.to(torch.int64)
     if nt.dim() == 2:
@@ -150,8 +260,36 @@ def normalizer_update(acc_sum, acc_sumsq, acc_count, num_acc, batch, count, max_
                                                 float(max_acc), _lib.stream_ptr()), 'hgn_normalizer_update')
 
 
+class _NormalizeFn(torch.autograd.Function):
+    """The running statistics are constants: the gradient goes to ``x`` alone.  They are updated in place by later
+    accumulations, so the backward pass uses the values this forward call normalised with (three tiny copies)."""
+
+    @staticmethod
+    def forward(ctx, x, acc_sum, acc_sumsq, acc_count, eps, inverse):
+        out = normalize(x.detach(), acc_sum, acc_sumsq, acc_count, eps, inverse)
+        ctx.cfg = (eps, inverse, x)
+        ctx.save_for_backward(acc_sum.detach().clone(), acc_sumsq.detach().clone(), acc_count.detach().clone())
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        eps, inverse, x = ctx.cfg
+        acc_sum, acc_sumsq, acc_count = ctx.saved_tensors
+        F = acc_sum.numel()
+        g = d_out.float().contiguous()
+        d_x = torch.empty_like(g)
+        _lib.check(_lib.lib().hgn_normalize_bwd(g.data_ptr(), g.numel() // F, F, acc_sum.data_ptr(), acc_sumsq.data_ptr(),
+                                                acc_count.data_ptr(), float(eps), 1 if inverse else 0, d_x.data_ptr(),
+                                                _lib.stream_ptr()), 'hgn_normalize_bwd')
+        return _like(d_x, x), None, None, None, None, None
+
+
 def normalize(x: torch.Tensor, acc_sum, acc_sumsq, acc_count, eps: float, inverse: bool = False) -> torch.Tensor:
+    """(x - mean) / std, or x * std + mean (``inverse``).  Differentiable with respect to ``x``; the statistics are constants."""
     _lib.require_gpu(x)
+    if _needs_grad(x):
+        return _NormalizeFn.apply(x, acc_sum, acc_sumsq, acc_count, eps, inverse)
     shape = x.shape
     F = acc_sum.numel()
     if x.dim() == 0 or shape[-1] != F and not (F == 1):
@@ -165,9 +303,27 @@ def normalize(x: torch.Tensor, acc_sum, acc_sumsq, acc_count, eps: float, invers
     return out
 
 
+class _Lincomb3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, ca, b, cb, c, cc):
+        ctx.cfg = (ca, cb, cc, a, b, c)
+        return lincomb3(a.detach(), ca, b.detach(), cb, c.detach() if c is not None else None, cc)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        ca, cb, cc, a, b, c = ctx.cfg
+        scaled = lambda k, ref: _like(g if k == 1.0 else g * k, ref)          # three scalings, no kernel of its own
+        return (scaled(ca, a) if ctx.needs_input_grad[0] else None, None, scaled(cb, b) if ctx.needs_input_grad[2] else None, None,
+                scaled(cc, c) if c is not None and ctx.needs_input_grad[4] else None, None)
+
+
 def lincomb3(a: torch.Tensor, ca: float, b: torch.Tensor, cb: float, c=None, cc: float = 0.0) -> torch.Tensor:
-    """(ca*a + cb*b) + cc*c, every product / sum rounded on its own (the reference's left-to-right fp32 order)."""
+    """(ca*a + cb*b) + cc*c, every product / sum rounded on its own (the reference's left-to-right fp32 order).  Differentiable with
+    respect to ``a``, ``b`` and ``c``."""
     _lib.require_gpu(a)
+    if _needs_grad(a, b, c):
+        return _Lincomb3Fn.apply(a, float(ca), b, float(cb), c, float(cc))
     dev = a.device
     a = a.float().contiguous()
     b = b.to(dev).float().contiguous()

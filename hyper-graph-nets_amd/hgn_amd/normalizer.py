@@ -28,8 +28,10 @@ class Normalizer(nn.Module):
         self._host_num_acc = 0              # host mirror of _num_accumulations: no device sync per call
 
     def forward(self, batched_data: Tensor, accumulate=True) -> Tensor:
+        """Differentiable with respect to ``batched_data`` (features.normalize); the running statistics are constants of the
+        result, so a tensor that requires grad is accumulated from its detached values."""
         if accumulate and self._host_num_acc < self._max_accumulations:
-            self._accumulate(batched_data)
+            self._accumulate(batched_data.detach() if batched_data.requires_grad else batched_data)
         return features.normalize(batched_data, self._acc_sum, self._acc_sum_squared, self._acc_count, self._eps)
 
     def inverse(self, normalized_batch_data: Tensor) -> Tensor:

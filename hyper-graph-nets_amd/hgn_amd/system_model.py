@@ -14,11 +14,20 @@ from typing import Dict, Tuple
 import torch
 from torch import nn, Tensor
 
-from . import features, ops, topology
+from . import _lib, features, ops, topology
 from . import rmp as _rmp
 from .modules import MeshGraphNet
 from .normalizer import Normalizer
 from .util import EdgeSet, MultiGraph, MultiGraphWithPos, NodeType, device
+
+
+def _value(t: Tensor) -> Tensor:
+    """The tensor as a plain value (what `node_dynamic` and `unnormalized_edges` carry): itself unless it requires grad."""
+    return t.detach() if t.requires_grad else t
+
+
+def _carries_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad for t in tensors)
 
 
 def _masked_mse(target: Tensor, output: Tensor, mask: Tensor) -> Tensor:
@@ -112,7 +121,14 @@ class AbstractSystemModel(nn.Module):
     def expand_graph(self, graph: MultiGraphWithPos, step: int, num_steps: int, is_training: bool) -> MultiGraph:
         """The optional stages between build_graph and the network, in the reference's order (flag.py:130-141,
         cylinder.py:108-119, plate.py:202-216): graph balancer first (appends the `balance` edge set, renormalises the mesh
-        edges), then remote message passing (hyper nodes + remote edge sets)."""
+        edges), then remote message passing (hyper nodes + remote edge sets).  Neither stage is differentiable with respect to the
+        positions (clusters, curvature and the hyper-node statistics are functions of them): a graph that carries position gradients
+        is refused instead of losing them."""
+        if (self._balancer or self._rmp) and _carries_grad(
+                graph.target_feature, graph.mesh_features, *graph.node_features, *(e.features for e in graph.edge_sets)):
+            raise _lib.HgnError('expand_graph: the graph balancer and remote message passing (connector) stages are not differentiable '
+                                'with respect to positions; build the graph from tensors that do not require grad, or under '
+                                'torch.no_grad(), or configure the model without these stages')
         if self._balancer:
             if self._refresh_due(step, num_steps, self._balance_frequency):
                 self._graph_balancer.reset_balancer()
@@ -189,12 +205,12 @@ class FlagModel(AbstractSystemModel):
                              receivers=receivers, senders=senders)
         # max - min incident edge length per node: both aggregates in one pass                      flag.py:100-115
         csr = topology.segment_csr(receivers, num_nodes, world_pos.device)
-        mm = ops.aggregate([length.unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
+        mm = ops.aggregate([_value(length).unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
         node_dynamic = self._node_dynamic_normalizer(features.lincomb3(mm[:, 0], 1.0, mm[:, 1], -1.0))
         return MultiGraphWithPos(
             node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
             target_feature=world_pos, mesh_features=mesh_pos, model_type=self._model_type, node_dynamic=node_dynamic,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=edge_features, receivers=receivers, senders=senders),
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             obstacle_nodes=None)
 
     def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
@@ -223,12 +239,12 @@ class FlagModel(AbstractSystemModel):
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
                              receivers=receivers, senders=senders)
         csr = topology.segment_csr(receivers, B * N, world_pos.device)
-        mm = ops.aggregate([length.unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
+        mm = ops.aggregate([_value(length).unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
         node_dynamic = self._node_dynamic_normalizer(features.lincomb3(mm[:, 0], 1.0, mm[:, 1], -1.0))
         return MultiGraphWithPos(
             node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
             target_feature=world_pos, mesh_features=mesh_pos, model_type=self._model_type, node_dynamic=node_dynamic,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=edge_features, receivers=receivers, senders=senders),
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             obstacle_nodes=None)
 
     def _loss_mask(self, data_frame):
@@ -311,7 +327,7 @@ class CylinderModel(AbstractSystemModel):
         return MultiGraphWithPos(
             node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
             mesh_features=mesh_pos, target_feature=velocity, model_type=self._model_type,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=edge_features, receivers=receivers, senders=senders),
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             node_dynamic=[], obstacle_nodes=None)
 
     def _loss_mask(self, data_frame):
@@ -387,10 +403,13 @@ class PlateModel(AbstractSystemModel):
         return connector if (self._rmp or connector == 'repeated') else 'none'        # plate.py:37-39
 
     def build_graph(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
-        """plate.py:69-200."""
+        """plate.py:69-200.  Not differentiable with respect to positions: the world edges are a radius query of them."""
         world_pos = inputs['world_pos'].to(device)
         mesh_pos = inputs['mesh_pos'].to(device)
         target_world_pos = inputs['target|world_pos'].to(device)
+        if _carries_grad(world_pos, mesh_pos, target_world_pos):
+            raise _lib.HgnError('PlateModel.build_graph is not differentiable with respect to positions (its world edges are a radius '
+                                'query of world_pos); pass tensors that do not require grad, or call it under torch.no_grad()')
         node_type = inputs['node_type'].to(device)
         num_nodes = node_type.shape[0]
         senders, receivers = self._mesh_edges(inputs['cells'], deform=True)

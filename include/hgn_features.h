@@ -76,6 +76,32 @@ int hgn_normalizer_update(float* acc_sum, float* acc_sumsq, float* acc_count, fl
 int hgn_normalize(const float* x, int64_t rows, int F, const float* acc_sum, const float* acc_sumsq,
                   const float* acc_count, float eps, int inverse, float* out, void* stream);
 
+/* ---- backward of the three feature kernels above (position gradients of a frame -> graph step) ---------------
+ * The statistics of the normaliser are constants of the graph: nothing flows into acc_sum / acc_sumsq / acc_count.
+ *
+ * hgn_rel_edge_features_bwd: d_feat [E, ldf] (nullable), d_len [E] (nullable) -> d_a [n_rows, da], d_b [n_rows, db]
+ *   (contiguous, each nullable).  With u = a[s]-a[r]: g = d_feat[0:da] + (d_feat[da] + d_len) * u/|u| is added to row s and
+ *   subtracted from row r (likewise for b, without d_len); an edge of zero length contributes nothing through the norm term.
+ *   Parallel over the n_rows nodes: (rowptr_s, perm_s) = CSR of the edges by sender, (rowptr_r, perm_r) by receiver, both as
+ *   hgn_csr_build makes them over the SAME id arrays (perm = position in the caller's edge order).  A node walks its outgoing,
+ *   then its incoming edges in CSR order and writes its row once: no float atomics, equal bits on every run, zeros for a node
+ *   without edges.  A node with more than 32 edges is summed by one wavefront, the others by one thread each; max_degree = an
+ *   upper bound of the edges (out + in) of any node, or < 0 when unknown (<= 32: the wavefront pass is not launched).
+ *   Ids outside [0, n_rows) / [0, E) are skipped, never dereferenced.  E = 0 or both gradients NULL: zero rows.
+ * hgn_node_features_bwd: d_out [N, ldo] -> d_cur, d_prev [N, d] (contiguous, each nullable): the velocity columns pass +d to
+ *   cur and -d to prev, zero on the rows the forward masked (vel_mask_type >= 0); the one-hot columns carry nothing.
+ * hgn_normalize_bwd: d_x = d_out / max(std, eps) (inverse = 0) or d_out * max(std, eps) (inverse = 1), std formed exactly as
+ *   in hgn_normalize. */
+int hgn_rel_edge_features_bwd(const float* d_feat, int64_t ldf, const float* d_len, const float* a, int64_t lda, int da,
+                              const float* b, int64_t ldb, int db, int64_t n_rows, const int64_t* senders,
+                              const int64_t* receivers, int64_t E, const int32_t* rowptr_s, const int32_t* perm_s,
+                              const int32_t* rowptr_r, const int32_t* perm_r, int64_t max_degree, float* d_a, float* d_b,
+                              void* stream);
+int hgn_node_features_bwd(const float* d_out, int64_t ldo, int d, int n_classes, int vel_first, const int64_t* node_type,
+                          int64_t ldt, int vel_mask_type, int64_t N, float* d_cur, float* d_prev, void* stream);
+int hgn_normalize_bwd(const float* d_out, int64_t rows, int F, const float* acc_sum, const float* acc_sumsq,
+                      const float* acc_count, float eps, int inverse, float* d_x, void* stream);
+
 /* ---- world edges by radius (plate.py:84-110) ---------------------------------------------------------------
  * Directed pairs (s, r), s != r, with |pos[s] - pos[r]| < radius, node_type[s] == sender_type, node_type[r] ==
  * receiver_type (a negative type = any), and (s, r) not adjacent in the mesh given as a CSR (nbr_rowptr [N+1],
