@@ -233,6 +233,63 @@ __global__ void radius_edges_kernel(const float* __restrict__ pos, long ld, int 
   if (!FILL && lane == 0) counts[s] = total;
 }
 
+// The same query over the disjoint union of n_graphs graphs of N nodes each (rows = n_graphs * N): sender row s of graph
+// b = s / N sweeps only the receivers [b*N, (b+1)*N) of its own graph, so the work is rows * N / 64 chunk iterations and no
+// pair crosses a graph boundary.  The neighbour CSR is the one of a single mesh (local ids), shared by every graph.
+template <bool FILL>
+__global__ void radius_edges_batch_kernel(const float* __restrict__ pos, long ld, int d,
+                                          const int64_t* __restrict__ node_type, long ldt, long rows, long N, float radius,
+                                          int sender_type, int receiver_type, const int* __restrict__ nbr_rowptr,
+                                          const int* __restrict__ nbr, int* __restrict__ counts,
+                                          const int* __restrict__ offsets, int64_t* __restrict__ senders,
+                                          int64_t* __restrict__ receivers) {
+  const int lane = threadIdx.x & 63;
+  const long s = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (s >= rows) return;
+  const bool active = sender_type < 0 || node_type[s * ldt] == sender_type;      // uniform per wave
+  if (!active) { if (!FILL && lane == 0) counts[s] = 0; return; }
+  const long g0 = (s / N) * N;                       // first row of the sender's graph
+  const long sl = s - g0;                            // local id: the row of the shared neighbour CSR
+  float ps[3];
+  for (int i = 0; i < 3; ++i) ps[i] = i < d ? pos[s * ld + i] : 0.f;
+  const int nb0 = nbr_rowptr ? nbr_rowptr[sl] : 0, nb1 = nbr_rowptr ? nbr_rowptr[sl + 1] : 0;
+  long base = FILL ? offsets[s] : 0;
+  int total = 0;
+  for (long r0 = 0; r0 < N; r0 += 64) {
+    const long rl = r0 + lane;                       // local receiver id, < N checked before any read
+    const long r = g0 + rl;
+    bool hit = false;
+    if (rl < N && r != s && (receiver_type < 0 || node_type[r * ldt] == receiver_type)) {
+      float q = 0.f;
+      for (int i = 0; i < 3; ++i) {
+        const float df = i < d ? ps[i] - pos[r * ld + i] : 0.f;
+        q = q + df * df;
+      }
+      hit = sqrtf(q) < radius;
+      if (hit)
+        for (int k = nb0; k < nb1; ++k)
+          if (nbr[k] == (int)rl) { hit = false; break; }
+    }
+    const unsigned long long m = __ballot(hit);
+    if (FILL && hit) {
+      const int before = __popcll(m & ((1ULL << lane) - 1ULL));
+      senders[base + before] = s;
+      receivers[base + before] = r;
+    }
+    const int c = __popcll(m);
+    base += c;
+    total += c;
+  }
+  if (!FILL && lane == 0) counts[s] = total;
+}
+
+// graph_offsets[b] = offsets[b * N] for b = 0 .. n_graphs (the last entry is the total)
+__global__ void graph_offsets_kernel(const int* __restrict__ offsets, long n_graphs, long N, int* __restrict__ graph_offsets) {
+  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b > n_graphs) return;
+  graph_offsets[b] = offsets[b * N];
+}
+
 // ----------------------------------------------------------------------------------------------------------
 // balanced Forman curvature (SDRF): one wavefront per edge / per candidate pair
 // ----------------------------------------------------------------------------------------------------------
@@ -681,6 +738,86 @@ extern "C" int hgn_radius_edges_fill(const float* pos, int64_t ld, int d, const 
                      node_type, (long)ldt, (long)N, radius, sender_type, receiver_type, nbr_rowptr, nbr, (int*)nullptr,
                      offsets, senders, receivers);
   return hgn_check_launch("hgn_radius_edges_fill");
+}
+
+// rows of the union, or -1 when the batch shape is refused (n_graphs < 1, nodes_per_graph < 0, more than 0x7ffffffe rows)
+static int64_t radius_batch_rows(int64_t n_graphs, int64_t nodes_per_graph) {
+  if (n_graphs < 1 || nodes_per_graph < 0) return -1;
+  if (nodes_per_graph > 0 && n_graphs > 0x7ffffffeLL / nodes_per_graph) return -1;
+  return n_graphs * nodes_per_graph;
+}
+
+static size_t radius_batch_counts_bytes(int64_t rows) { return up256((size_t)(rows + 1) * 4); }
+
+extern "C" int hgn_radius_edges_batch_workspace_bytes(int64_t n_graphs, int64_t nodes_per_graph, size_t* bytes) {
+  const int64_t rows = radius_batch_rows(n_graphs, nodes_per_graph);
+  if (!bytes || rows < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_workspace_bytes: bad size (n_graphs >= 1, nodes_per_graph >= 0, "
+                                   "n_graphs * nodes_per_graph <= 0x7ffffffe)");
+  size_t t = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum<int*, int*>(nullptr, t, nullptr, nullptr, (int)(rows + 1));
+  *bytes = radius_batch_counts_bytes(rows) + up256(t) + 256;
+  return HGN_OK;
+}
+
+extern "C" int hgn_radius_edges_batch_count(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                            int64_t n_graphs, int64_t nodes_per_graph, float radius, int sender_type,
+                                            int receiver_type, const int32_t* nbr_rowptr, const int32_t* nbr,
+                                            int32_t* offsets, int32_t* graph_offsets, int64_t* total, void* workspace,
+                                            size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int64_t rows = radius_batch_rows(n_graphs, nodes_per_graph);
+  if (rows < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_count: bad batch shape (n_graphs >= 1, nodes_per_graph >= 0, "
+                                   "n_graphs * nodes_per_graph <= 0x7ffffffe)");
+  if (!radius_args_ok(pos, ld, d, node_type, ldt, rows, radius, nbr_rowptr, nbr))
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_count: bad argument");
+  if (!offsets || !total) return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_count: null output");
+  size_t need = 0;
+  if (hgn_radius_edges_batch_workspace_bytes(n_graphs, nodes_per_graph, &need) != HGN_OK || !workspace || ws_bytes < need)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_count: workspace missing or too small");
+  *total = 0;
+  ProfScope ps(13, (double)rows, stream);
+  int* counts = (int*)workspace;
+  void* temp = (char*)workspace + radius_batch_counts_bytes(rows);
+  size_t tb = need - radius_batch_counts_bytes(rows);
+  if (hipMemsetAsync(counts, 0, (size_t)(rows + 1) * 4, stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_batch_count memset");
+  if (rows > 0)
+    hipLaunchKernelGGL(radius_edges_batch_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, pos, (long)ld, d,
+                       node_type, (long)ldt, (long)rows, (long)nodes_per_graph, radius, sender_type, receiver_type, nbr_rowptr,
+                       nbr, counts, (const int*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
+  if (hipcub::DeviceScan::ExclusiveSum(temp, tb, counts, offsets, (int)(rows + 1), stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_batch_count scan");
+  if (graph_offsets)
+    hipLaunchKernelGGL(graph_offsets_kernel, dim3((unsigned)((n_graphs + 256) / 256)), dim3(256), 0, stream,
+                       (const int*)offsets, (long)n_graphs, (long)nodes_per_graph, graph_offsets);
+  int host_total = 0;
+  if (hipMemcpyAsync(&host_total, offsets + rows, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_batch_count readback");
+  *total = host_total;
+  return hgn_check_launch("hgn_radius_edges_batch_count");
+}
+
+extern "C" int hgn_radius_edges_batch_fill(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                           int64_t n_graphs, int64_t nodes_per_graph, float radius, int sender_type,
+                                           int receiver_type, const int32_t* nbr_rowptr, const int32_t* nbr,
+                                           const int32_t* offsets, int64_t* senders, int64_t* receivers, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int64_t rows = radius_batch_rows(n_graphs, nodes_per_graph);
+  if (rows < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_fill: bad batch shape (n_graphs >= 1, nodes_per_graph >= 0, "
+                                   "n_graphs * nodes_per_graph <= 0x7ffffffe)");
+  if (!radius_args_ok(pos, ld, d, node_type, ldt, rows, radius, nbr_rowptr, nbr) || !offsets)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_fill: bad argument");
+  if (rows == 0) return HGN_OK;
+  if (!senders || !receivers) return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_batch_fill: null output");
+  ProfScope ps(13, (double)rows, stream);
+  hipLaunchKernelGGL(radius_edges_batch_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, pos, (long)ld, d,
+                     node_type, (long)ldt, (long)rows, (long)nodes_per_graph, radius, sender_type, receiver_type, nbr_rowptr, nbr,
+                     (int*)nullptr, offsets, senders, receivers);
+  return hgn_check_launch("hgn_radius_edges_batch_fill");
 }
 
 extern "C" int hgn_forman_curvature(const float* A, const float* A2, const float* d_in, const float* d_out, int64_t N,

@@ -369,3 +369,42 @@ def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, send
         _lib.check(L.hgn_radius_edges_fill(*args, offsets.data_ptr(), s.data_ptr(), r.data_ptr(), _lib.stream_ptr()),
                    'hgn_radius_edges_fill')
     return s, r
+
+
+def radius_edges_batch(pos: torch.Tensor, node_type: torch.Tensor, n_graphs: int, radius: float, sender_type: int,
+                       receiver_type: int, nbr_rowptr=None, nbr=None):
+    """``radius_edges`` over the disjoint union of ``n_graphs`` graphs of equal size in one query (not in the reference, which
+    runs plate.py:84-110 per frame and concatenates, MeshSimulator.py:159-234): ``pos`` / ``node_type`` hold the B*N rows of the
+    union, graph b owns rows [b*N, (b+1)*N); no pair crosses a graph; ``nbr_rowptr`` / ``nbr`` is the neighbour CSR of ONE mesh
+    (local ids) shared by all graphs.  Union ids in ascending (sender, receiver) order = the per-graph results shifted by b*N and
+    concatenated.  One host read-back for the whole batch.
+    -> (senders, receivers) int64 and graph_offsets [B+1] int32 (edges before graph b; the last entry is the total)."""
+    _lib.require_gpu(pos)
+    dev = pos.device
+    pos = _f32_rows(pos)
+    nt = node_type.to(device=dev, dtype=torch.int64)
+    if nt.dim() == 2:
+        nt = nt[:, 0]
+    rows, B = pos.shape[0], int(n_graphs)
+    if B < 1 or rows % B or nt.shape[0] != rows:
+        raise ValueError(f'radius_edges_batch: {rows} position rows / {nt.shape[0]} node types do not split into {B} graphs of equal size')
+    N = rows // B
+    ldt = nt.stride(0) if rows > 1 else 1
+    L = _lib.lib()
+    nb = C.c_size_t(0)
+    _lib.check(L.hgn_radius_edges_batch_workspace_bytes(B, N, C.byref(nb)), 'hgn_radius_edges_batch_workspace_bytes')
+    ws = _workspace(dev, nb.value, 'radius')
+    offsets = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    graph_offsets = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    total = C.c_int64(0)
+    args = (pos.data_ptr(), _ld(pos), pos.shape[1], nt.data_ptr(), ldt, B, N, float(radius), int(sender_type),
+            int(receiver_type), nbr_rowptr.data_ptr() if nbr_rowptr is not None else None,
+            nbr.data_ptr() if nbr is not None else None)
+    _lib.check(L.hgn_radius_edges_batch_count(*args, offsets.data_ptr(), graph_offsets.data_ptr(), C.byref(total),
+                                              ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'hgn_radius_edges_batch_count')
+    s = torch.empty(total.value, dtype=torch.int64, device=dev)
+    r = torch.empty(total.value, dtype=torch.int64, device=dev)
+    if total.value:
+        _lib.check(L.hgn_radius_edges_batch_fill(*args, offsets.data_ptr(), s.data_ptr(), r.data_ptr(), _lib.stream_ptr()),
+                   'hgn_radius_edges_batch_fill')
+    return s, r, graph_offsets

@@ -239,7 +239,7 @@ class _ClusterTopology:
         members = torch.cat([torch.as_tensor(c).long() for c in clusters]).to(dev)
         label = torch.repeat_interleave(torch.arange(K), torch.tensor(sizes)).to(dev)
         hyper = label + num_nodes
-        self.K, self.N, self.M = K, num_nodes, int(members.numel())
+        self.K, self.N, self.M, self.B = K, num_nodes, int(members.numel()), 1           # B: graphs the topology spans
         self.sizes = torch.tensor(sizes, dtype=torch.float32, device=dev)
         self.members, self.label, self.hyper = members, label, hyper
         csr = topology.CSR(label, K)
@@ -258,6 +258,33 @@ class _ClusterTopology:
         s, r = idx[:, 0].to(dev), idx[:, 1].to(dev)
         self.inter_s = torch.cat([s, r]).contiguous()
         self.inter_r = torch.cat([r, s]).contiguous()
+
+    @classmethod
+    def batched(cls, one: '_ClusterTopology', B: int) -> '_ClusterTopology':
+        """The topology of the disjoint union of B graphs that share one clustering (not in the reference, which connects every
+        frame on its own and concatenates, MeshSimulator.py:159-234): members of graph b are shifted by b*N, hyper node k of graph
+        b has union id B*N + b*K + k (batching.batch_graphs with reference_compat=False), the inter-cluster pairs are replicated
+        per graph, and every edge list is graph-major -- the order in which the per-frame sets concatenate.  K, N stay per graph;
+        M, sizes, members, label, hyper, the CSR and the edge ids describe the union (B*K segments, B*M members)."""
+        self = cls.__new__(cls)
+        K, N, M, dev = one.K, one.N, one.M, one.members.device
+        g = torch.arange(B, device=dev)
+        members = (one.members.repeat(B) + (g * N).repeat_interleave(M)).contiguous()
+        label = (one.label.repeat(B) + (g * K).repeat_interleave(M)).contiguous()
+        hyper = label + B * N
+        self.K, self.N, self.M, self.B = K, N, B * M, B
+        self.sizes = one.sizes.repeat(B)
+        self.members, self.label, self.hyper = members, label, hyper
+        csr = topology.CSR(label, B * K)
+        self.node_perm = members[csr.perm.long()].to(torch.int32).contiguous()
+        self.csr = csr
+        self.up_down_s = torch.cat([hyper, members]).contiguous()
+        self.up_down_r = torch.cat([members, hyper]).contiguous()
+        # one graph's inter-cluster edges are [s ; r] -> [r ; s] in local hyper ids N + k: shift them to B*N + b*K + k
+        shift = (g * K).repeat_interleave(one.inter_s.shape[0]) + (B - 1) * N
+        self.inter_s = (one.inter_s.repeat(B) + shift).contiguous()
+        self.inter_r = (one.inter_r.repeat(B) + shift).contiguous()
+        return self
 
 
 class AbstractConnector:
@@ -286,22 +313,27 @@ class HierarchicalConnector(AbstractConnector):
         super().initialize(intra, inter, hyper)
         return ['intra_cluster_to_mesh', 'intra_cluster_to_cluster', 'inter_cluster']
 
-    def _cluster_topology(self, clusters, neighbors, N, dev) -> _ClusterTopology:
-        key = (id(clusters), len(clusters), N, id(neighbors))
+    def _cluster_topology(self, clusters, neighbors, N, dev, n_graphs: int = 1) -> _ClusterTopology:
+        key = (id(clusters), len(clusters), N, id(neighbors), n_graphs)
         if self._topo_key != key:
             self._topo = _ClusterTopology(clusters, neighbors, N, self._fully_connect, dev)
+            if n_graphs > 1:
+                self._topo = _ClusterTopology.batched(self._topo, n_graphs)
             self._topo_key = key
             self._keep = (clusters, neighbors)           # the ids in the key stay valid while we hold the objects
         return self._topo
 
     def run(self, graph: MultiGraphWithPos, clusters: List[Tensor], neighbors: List[Tensor], is_training: bool,
-            noise: Optional[Tensor] = None) -> MultiGraph:
+            noise: Optional[Tensor] = None, n_graphs: int = 1) -> MultiGraph:
+        """``n_graphs`` > 1: ``graph`` is the disjoint union of that many graphs of one mesh (build_graph_batch) and ``clusters`` /
+        ``neighbors`` describe ONE of them; the same passes then run once over the union (_ClusterTopology.batched): one
+        segment-mean pass, one relative-feature pass per remote set, one max pass for the spreads; noise is [B*K, C]."""
         if graph.model_type not in ('flag', 'plate'):
             raise Exception('Model type is not specified in RippleNodeConnector.')       # abstract_connector.py:97
         nf = graph.node_features.to(device)
-        N = nf.shape[0]
+        N = nf.shape[0] // n_graphs
         cf = torch.cat((graph.target_feature.to(device), graph.mesh_features.to(device)), dim=1)   # :29
-        t = self._cluster_topology(clusters, neighbors, N, cf.device)
+        t = self._cluster_topology(clusters, neighbors, N, cf.device, n_graphs)
         C = cf.shape[1]
         # cluster means of [clustering features | node features]: one segment-mean pass over the member rows
         both = torch.cat((cf, nf), dim=1)
@@ -341,14 +373,14 @@ class HierarchicalConnector(AbstractConnector):
 class MultigraphConnector(HierarchicalConnector):
     """multigraph_connector.py:11-89: the hierarchical expansion folded into ONE edge set -- node rows get a 2-way and edge
     rows a 4-way one-hot tag (mesh / inter-cluster / to-cluster / to-mesh) and all remote edges are appended to
-    'mesh_edges'; 'world_edges' passes through.  Pure data movement on top of HierarchicalConnector.run."""
+    'mesh_edges'; 'world_edges' passes through where the model has them.  Pure data movement on top of HierarchicalConnector.run."""
 
     def initialize(self, intra, inter, hyper):
         AbstractConnector.initialize(self, intra, inter, hyper)
         return []
 
-    def run(self, graph, clusters, neighbors, is_training, noise=None) -> MultiGraph:
-        g = super().run(graph, clusters, neighbors, is_training, noise)
+    def run(self, graph, clusters, neighbors, is_training, noise=None, n_graphs: int = 1) -> MultiGraph:
+        g = super().run(graph, clusters, neighbors, is_training, noise, n_graphs)
         nf, hnf = g.node_features
 
         def tag(x, k, n):
@@ -358,11 +390,21 @@ class MultigraphConnector(HierarchicalConnector):
         by_name = {e.name: e for e in g.edge_sets}
         order = ('mesh_edges', 'inter_cluster', 'intra_cluster_to_cluster', 'intra_cluster_to_mesh')
         parts = [by_name[n] for n in order]
+
+        def merge(rows):
+            """The four parts behind one another; for a union of graphs, graph by graph (every part is graph-major with the same
+            number of rows per graph), which is the order in which per-frame merged sets concatenate."""
+            if n_graphs == 1:
+                return torch.cat(rows, dim=0)
+            return torch.cat([x.reshape((n_graphs, x.shape[0] // n_graphs) + tuple(x.shape[1:])) for x in rows], dim=1).flatten(0, 1)
         merged = EdgeSet(name='mesh_edges',
-                         features=torch.cat([tag(e.features, k, 4) for k, e in enumerate(parts)], dim=0),
-                         senders=torch.cat([e.senders.to(device) for e in parts], dim=0),
-                         receivers=torch.cat([e.receivers.to(device) for e in parts], dim=0))
-        return MultiGraph(node_features=[tag(nf, 0, 2), tag(hnf, 1, 2)], edge_sets=[merged, by_name['world_edges']])
+                         features=merge([tag(e.features, k, 4) for k, e in enumerate(parts)]),
+                         senders=merge([e.senders.to(device) for e in parts]),
+                         receivers=merge([e.receivers.to(device) for e in parts]))
+        # 'world_edges' alone passes through (multigraph_connector.py:83: any other set, 'balance' included, is dropped), and only
+        # where the model has them: the reference indexes the set unconditionally (:30) and so fails for the flag model
+        rest = [e for e in g.edge_sets if e.name == 'world_edges']
+        return MultiGraph(node_features=[tag(nf, 0, 2), tag(hnf, 1, 2)], edge_sets=[merged] + rest)
 
 
 class RemoteMessagePassing:
@@ -386,6 +428,37 @@ class RemoteMessagePassing:
                 self._clusters = self._clustering_algorithm.run(graph)
             self._neighbors = self._clustering_algorithm.neigboring_clusters
         return self._node_connector.run(graph, self._clusters, self._neighbors, is_training)
+
+    def create_graph_batch(self, graph: MultiGraphWithPos, n_graphs: int, is_training: bool) -> MultiGraph:
+        """create_graph for the disjoint union of ``n_graphs`` frames of one mesh (build_graph_batch): the clusters come, once,
+        from the first frame of the batch (through remove_obstacles where there are obstacle nodes); the connector then runs once
+        over the union."""
+        graph = graph._replace(node_features=graph.node_features[0])
+        if self._clusters is None:
+            first = self._first_frame_graph(graph, n_graphs)
+            if first.obstacle_nodes is not None:
+                self.remove_obstacles(first)
+            else:
+                self._clusters = self._clustering_algorithm.run(first)
+            self._neighbors = self._clustering_algorithm.neigboring_clusters
+        return self._node_connector.run(graph, self._clusters, self._neighbors, is_training, n_graphs=n_graphs)
+
+    @staticmethod
+    def _first_frame_graph(graph: MultiGraphWithPos, n_graphs: int) -> MultiGraphWithPos:
+        """Graph 0 of a union of ``n_graphs`` graphs of one mesh: rows [0, N) and the first E / B mesh edges (graph-major lists:
+        those of graph 0, in local ids)."""
+        N = graph.node_features.shape[0] // n_graphs
+
+        def head(es):
+            if es is None:
+                return None
+            E = es.senders.shape[0] // n_graphs
+            return EdgeSet(es.name, es.features[:E], es.senders[:E], es.receivers[:E])
+        rows = lambda t: t[:N] if torch.is_tensor(t) else t
+        return graph._replace(node_features=graph.node_features[:N], target_feature=graph.target_feature[:N],
+                              mesh_features=graph.mesh_features[:N], node_dynamic=rows(graph.node_dynamic),
+                              obstacle_nodes=rows(graph.obstacle_nodes), unnormalized_edges=head(graph.unnormalized_edges),
+                              edge_sets=[head(e) for e in graph.edge_sets if e.name == 'mesh_edges'])
 
     def remove_obstacles(self, graph: MultiGraphWithPos) -> None:
         """remote_message_passing.py:82-137: cluster only the non-obstacle nodes (the obstacle block is contiguous, at

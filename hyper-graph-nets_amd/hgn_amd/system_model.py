@@ -91,11 +91,14 @@ class AbstractSystemModel(nn.Module):
     def __getstate__(self):
         """The reference pickles the whole system model at every checkpoint (MeshSimulator.py:492-493 `pickle.dump(self)`, with
         `_network` inside) and deep-copies it for evaluation.  Captured HIP graphs (the rollout replay cache) and the per-mesh
-        edge cache are run-time state, not model state: a copy starts without them and captures again on its own device."""
+        edge caches are run-time state, not model state: a copy starts without them and captures again on its own device."""
         state = super().__getstate__()
         state['_fwd_cache'] = None
         state['_cells_key'] = None
         state['_cells_edges'] = None
+        for name in ('_batch_edges_key', '_batch_edges'):                # the union's mesh edges: rebuilt from the mesh on first use
+            if name in state:
+                state[name] = None
         return state
 
     def _select_architecture(self, connector):
@@ -111,6 +114,36 @@ class AbstractSystemModel(nn.Module):
             s, r, _ = features.cells_to_edges(cells.to(device), deform)
             self._cells_key, self._cells_edges = cells, (s.contiguous(), r.contiguous())
         return self._cells_edges
+
+    def _union_mesh_edges(self, senders: Tensor, receivers: Tensor, n_graphs: int, num_nodes: int):
+        """Mesh edges of the disjoint union of ``n_graphs`` copies of one mesh: the ids of copy b are shifted by b * num_nodes
+        (what batching.batch_graphs does), graph-major.  Built once per (mesh, batch size, node count)."""
+        key = getattr(self, '_batch_edges_key', None)                    # (B, N, the mesh's sender tensor: _mesh_edges caches it)
+        if key is None or key[0] != n_graphs or key[1] != num_nodes or key[2] is not senders:
+            off = (torch.arange(n_graphs, device=senders.device) * num_nodes).repeat_interleave(senders.shape[0])
+            self._batch_edges = ((senders.repeat(n_graphs) + off).contiguous(), (receivers.repeat(n_graphs) + off).contiguous())
+            self._batch_edges_key = (n_graphs, num_nodes, senders)
+        return self._batch_edges
+
+    @staticmethod
+    def _union_rows(inputs: Dict, name: str, n_graphs: int, num_nodes: int) -> Tensor:
+        """``inputs[name]`` as the [B*N, .] rows of the union: a [B, N, .] series is flattened, a shared [N, .] entry (one mesh for
+        all frames) is repeated."""
+        t = inputs[name].to(device)
+        if t.dim() == 2:
+            t = t.unsqueeze(0).expand(n_graphs, num_nodes, -1)
+        return t.reshape(n_graphs * num_nodes, -1).contiguous()
+
+    @staticmethod
+    def flatten_frames(inputs: Dict) -> Dict:
+        """B stacked frames of one mesh -> the rows of their disjoint union: every per-node series [B, N, .] becomes [B*N, .]
+        (frame b owns rows [b*N, (b+1)*N), the row order of build_graph_batch); entries shared by all frames (`cells`, a `mesh_pos`
+        given once as [N, .]) are handed on as the same objects.  B and N are read from `node_type` [B, N, 1].  training_step,
+        validation_step, get_target, update and the loss mask are element-wise over rows, so they take the result together with the
+        graph of build_graph_batch / expand_graph_batch unchanged."""
+        B, N = inputs['node_type'].shape[0], inputs['node_type'].shape[1]
+        return {name: (t.reshape(B * N, -1) if name != 'cells' and torch.is_tensor(t) and t.dim() == 3 and tuple(t.shape[:2]) == (B, N)
+                       else t) for name, t in inputs.items()}
 
     @staticmethod
     def _refresh_due(step: int, num_steps: int, frequency) -> bool:
@@ -138,6 +171,31 @@ class AbstractSystemModel(nn.Module):
                 self._remote_graph.reset_clusters()
             graph = self._remote_graph.create_graph(graph, is_training)
         return graph
+
+    def expand_graph_batch(self, graph: MultiGraphWithPos, n_graphs: int, step: int, num_steps: int, is_training: bool) -> MultiGraph:
+        """Not in the reference (which expands every frame of a batch on its own and concatenates, MeshSimulator.py:159-234):
+        ``expand_graph`` for the union of ``n_graphs`` frames that build_graph_batch returns.  Without a connector the union comes
+        back as a MultiGraph.  With one, remote message passing runs ONCE over the union: the cluster labels are computed as in
+        expand_graph (once per period, `_refresh_due`), from the first frame of the batch (rows [0, N) with its mesh edges; the
+        reference also clusters once per trajectory, from the frame that arrives first), every graph gets its own K hyper nodes
+        (hyper node k of graph b has union id B*N + b*K + k, the mapping of batching.batch_graphs) and each remote edge set lists
+        its edges graph by graph -- ids and order of batch_graphs over the per-frame expand_graph results.
+        Semantic difference to B expand_graph calls: each normaliser accumulates ONCE, with the statistics of the whole batch, and
+        `hyper_noise` is drawn once per call for all B*K hyper nodes.
+        Out of scope: a configured graph balancer (HgnError) and meshes that differ within one batch.  Like expand_graph, a
+        connector refuses a graph that carries position gradients."""
+        if self._balancer:
+            raise _lib.HgnError('expand_graph_batch: the graph balancer stage has no batched form; expand the frames one by one with '
+                                'expand_graph and batch them with batching.batch_graphs, or configure the model without a balancer')
+        if not self._rmp:
+            return MultiGraph(node_features=graph.node_features, edge_sets=graph.edge_sets)
+        if _carries_grad(graph.target_feature, graph.mesh_features, *graph.node_features, *(e.features for e in graph.edge_sets)):
+            raise _lib.HgnError('expand_graph_batch: the remote message passing (connector) stage is not differentiable with respect to '
+                                'positions; build the graph from tensors that do not require grad, or under torch.no_grad(), or '
+                                'configure the model without this stage')
+        if self._refresh_due(step, num_steps, self._rmp_frequency):
+            self._remote_graph.reset_clusters()
+        return self._remote_graph.create_graph_batch(graph, int(n_graphs), is_training)
 
     def forward(self, graph):
         # Rollout / evaluation (no gradients, on the GPU): the network is replayed from a HIP graph captured per topology, from the
@@ -227,13 +285,7 @@ class FlagModel(AbstractSystemModel):
         mesh_pos = (mesh_pos if mesh_pos.dim() == 3 else mesh_pos.unsqueeze(0).expand(B, N, -1)).reshape(B * N, -1).contiguous()
         node_type = inputs['node_type'].to(device).reshape(B * N, -1)
         world_pos = world_pos.reshape(B * N, 3)
-        s1, r1 = self._mesh_edges(inputs['cells'])
-        key = (B, N, s1.data_ptr())
-        if getattr(self, '_batch_edges_key', None) != key:               # batched topology: once per (mesh, batch size)
-            off = (torch.arange(B, device=s1.device) * N).repeat_interleave(s1.shape[0])
-            self._batch_edges = ((s1.repeat(B) + off).contiguous(), (r1.repeat(B) + off).contiguous())
-            self._batch_edges_key = key
-        senders, receivers = self._batch_edges
+        senders, receivers = self._union_mesh_edges(*self._mesh_edges(inputs['cells']), B, N)
         node_features = features.node_features(world_pos, prev, node_type, self._TYPE_MAP, 2)
         edge_features, length = features.rel_edge_features(world_pos, mesh_pos, senders, receivers, want_len=True)
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
@@ -330,6 +382,30 @@ class CylinderModel(AbstractSystemModel):
             unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             node_dynamic=[], obstacle_nodes=None)
 
+    def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
+        """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames
+        of ONE mesh -- `velocity`, `node_type` with a leading batch dimension [B, N, .], `mesh_pos` [N, 2] or [B, N, 2], `cells`
+        [F, 3] -- become the disjoint union of B graphs in the handful of launches a single frame takes (node ids of frame b are
+        offset by b*N, as batching.batch_graphs does); the fields are those build_graph fills.  Differentiable with respect to
+        `velocity` exactly as build_graph is.
+        Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
+        batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
+        velocity = inputs['velocity'].to(device)
+        B, N = velocity.shape[0], velocity.shape[1]
+        velocity = velocity.reshape(B * N, -1)
+        mesh_pos = self._union_rows(inputs, 'mesh_pos', B, N)
+        node_type = inputs['node_type'].to(device).reshape(B * N, -1)
+        node_features = features.node_features(velocity, None, node_type, self._TYPE_MAP, 4)
+        senders, receivers = self._union_mesh_edges(*self._mesh_edges(inputs['cells']), B, N)
+        edge_features, _ = features.rel_edge_features(mesh_pos, None, senders, receivers)
+        mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
+                             receivers=receivers, senders=senders)
+        return MultiGraphWithPos(
+            node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
+            mesh_features=mesh_pos, target_feature=velocity, model_type=self._model_type,
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
+            node_dynamic=[], obstacle_nodes=None)
+
     def _loss_mask(self, data_frame):
         t = data_frame['node_type'].to(device)[:, 0]
         return torch.logical_or(torch.eq(t, NodeType.OUTFLOW.value), torch.eq(t, NodeType.NORMAL.value))
@@ -414,12 +490,9 @@ class PlateModel(AbstractSystemModel):
         num_nodes = node_type.shape[0]
         senders, receivers = self._mesh_edges(inputs['cells'], deform=True)
         # world edges: obstacle -> normal pairs closer than the radius that are not mesh edges          plate.py:84-110
-        csr = topology.segment_csr(receivers, num_nodes, world_pos.device)        # neighbours of n = senders of its edges
-        if getattr(self, '_nbr_key', None) is not senders:
-            self._nbr = senders[csr.perm.long()].to(torch.int32).contiguous()
-            self._nbr_key = senders
+        nbr_rowptr = self._mesh_neighbours(senders, receivers, num_nodes, world_pos.device)
         world_senders, world_receivers = features.radius_edges(world_pos, node_type, self._RADIUS, NodeType.OBSTACLE.value,
-                                                                NodeType.NORMAL.value, csr.rowptr, self._nbr)
+                                                                NodeType.NORMAL.value, nbr_rowptr, self._nbr)
         world_edge_features, _ = features.rel_edge_features(world_pos, None, world_senders, world_receivers)
         world_edges = EdgeSet(name='world_edges', features=self._world_edge_normalizer(world_edge_features, is_training),
                               receivers=world_receivers, senders=world_senders)
@@ -427,6 +500,58 @@ class PlateModel(AbstractSystemModel):
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(mesh_edge_features, is_training),
                              receivers=receivers, senders=senders)
         # one-hot(3) | velocity of the kinematic (obstacle) nodes, zero elsewhere                      plate.py:186-195
+        node_features = features.node_features(target_world_pos, world_pos, node_type, self._TYPE_MAP, 3, vel_first=False,
+                                               vel_mask_type=NodeType.OBSTACLE.value)
+        obstacle_nodes = torch.eq(node_type[:, 0], NodeType.OBSTACLE.value)
+        return MultiGraphWithPos(
+            node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges, world_edges],
+            mesh_features=mesh_pos, target_feature=world_pos, model_type=self._model_type,
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=mesh_edge_features, receivers=receivers,
+                                       senders=senders),
+            node_dynamic=None, obstacle_nodes=obstacle_nodes)
+
+    def _mesh_neighbours(self, senders: Tensor, receivers: Tensor, num_nodes: int, dev) -> Tensor:
+        """Neighbour CSR of ONE mesh for the radius query: -> rowptr; `self._nbr` = the senders of every node's incoming edges,
+        cached while the same mesh edges come in."""
+        csr = topology.segment_csr(receivers, num_nodes, dev)                      # neighbours of n = senders of its edges
+        if getattr(self, '_nbr_key', None) is not senders:
+            self._nbr = senders[csr.perm.long()].to(torch.int32).contiguous()
+            self._nbr_key = senders
+        return csr.rowptr
+
+    def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
+        """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames
+        of ONE mesh -- `world_pos`, `target|world_pos`, `node_type` with a leading batch dimension [B, N, .], `mesh_pos` [N, 3] or
+        [B, N, 3], `cells` [F, 4] -- become the disjoint union of B graphs (node ids of frame b are offset by b*N, as
+        batching.batch_graphs does); the fields are those build_graph fills, `obstacle_nodes` is [B*N].  The `world_edges` of all
+        frames come from ONE radius query over the union (features.radius_edges_batch with the cached neighbour CSR of the one
+        mesh): one host synchronisation for the batch instead of one per frame, and no pair crosses a frame.  Like build_graph,
+        not differentiable with respect to positions.
+        Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
+        batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
+        world_pos = inputs['world_pos'].to(device)
+        mesh_pos = inputs['mesh_pos'].to(device)
+        target_world_pos = inputs['target|world_pos'].to(device)
+        if _carries_grad(world_pos, mesh_pos, target_world_pos):
+            raise _lib.HgnError('PlateModel.build_graph_batch is not differentiable with respect to positions (its world edges are a '
+                                'radius query of world_pos); pass tensors that do not require grad, or call it under torch.no_grad()')
+        B, N = world_pos.shape[0], world_pos.shape[1]
+        world_pos = world_pos.reshape(B * N, 3)
+        target_world_pos = target_world_pos.reshape(B * N, 3)
+        mesh_pos = self._union_rows(inputs, 'mesh_pos', B, N)
+        node_type = inputs['node_type'].to(device).reshape(B * N, -1)
+        senders1, receivers1 = self._mesh_edges(inputs['cells'], deform=True)
+        senders, receivers = self._union_mesh_edges(senders1, receivers1, B, N)
+        # world edges of all frames in one query; mesh neighbours are excluded through the CSR of the ONE mesh   plate.py:84-110
+        nbr_rowptr = self._mesh_neighbours(senders1, receivers1, N, world_pos.device)
+        world_senders, world_receivers, _ = features.radius_edges_batch(
+            world_pos, node_type, B, self._RADIUS, NodeType.OBSTACLE.value, NodeType.NORMAL.value, nbr_rowptr, self._nbr)
+        world_edge_features, _ = features.rel_edge_features(world_pos, None, world_senders, world_receivers)
+        world_edges = EdgeSet(name='world_edges', features=self._world_edge_normalizer(world_edge_features, is_training),
+                              receivers=world_receivers, senders=world_senders)
+        mesh_edge_features, _ = features.rel_edge_features(world_pos, mesh_pos, senders, receivers)
+        mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(mesh_edge_features, is_training),
+                             receivers=receivers, senders=senders)
         node_features = features.node_features(target_world_pos, world_pos, node_type, self._TYPE_MAP, 3, vel_first=False,
                                                vel_mask_type=NodeType.OBSTACLE.value)
         obstacle_nodes = torch.eq(node_type[:, 0], NodeType.OBSTACLE.value)

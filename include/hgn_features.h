@@ -11,6 +11,8 @@
  *   model/flag.py:68-74, cylinder.py:67-76, plate.py:75-79,186-195
  *                                    velocity + one-hot node features          -> hgn_node_features
  *   model/plate.py:84-110            world edges (cdist + masks + nonzero)      -> hgn_radius_edges_count/_fill
+ *   model/plate.py:84-110 per frame + algorithms/MeshSimulator.py:159-234 (_get_batched)
+ *                                    world edges of a batch of frames, one query -> hgn_radius_edges_batch_count/_fill
  *   graph_balancer/ricci.py:128-301  balanced Forman curvature kernels (SDRF)   -> hgn_forman_curvature/_post_delta
  *   model/flag.py:178,188, cylinder.py:163,171  target / integrator arithmetic   -> hgn_lincomb3
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
@@ -121,6 +123,34 @@ int hgn_radius_edges_fill(const float* pos, int64_t ld, int d, const int64_t* no
                           float radius, int sender_type, int receiver_type, const int32_t* nbr_rowptr,
                           const int32_t* nbr, const int32_t* offsets, int64_t* senders, int64_t* receivers,
                           void* stream);
+
+/* ---- world edges of a whole batch of frames (plate.py:84-110 once per frame, MeshSimulator.py:159-234 for the union) ----
+ * The reference builds the world edges of every frame of a batch on its own and then concatenates the graphs with ids
+ * shifted by i * num_nodes (_get_batched).  Here the radius query runs once over the disjoint union of n_graphs graphs of
+ * nodes_per_graph (N) nodes each: pos / node_type hold the B*N rows of the union, graph b owns rows [b*N, (b+1)*N).
+ * A pair (s, r) is reported only if both ends lie in the same graph.  nbr_rowptr [N+1] / nbr is the CSR of ONE mesh in
+ * local ids (nullable), shared by all graphs (frames of one trajectory share `cells`); the exclusion is tested on
+ * (s - b*N, r - b*N), no union CSR is built.  Types, radius and the distance expression (sqrtf of the fp32 sum of squares,
+ * < radius) are those of hgn_radius_edges_count.  Output: union ids in ascending (s, r) order = the concatenation over b of
+ * what hgn_radius_edges_count/_fill return for graph b, shifted by b*N.
+ * _count fills offsets [B*N+1] (device int32, exclusive prefix of the per-sender counts, offsets[B*N] = total) and, when
+ * graph_offsets is not NULL, graph_offsets [B+1] (device int32: graph_offsets[b] = offsets[b*N] = edges before graph b,
+ * graph_offsets[B] = total), and returns the total on the HOST: ONE stream synchronisation for the batch instead of B.
+ * _fill writes senders / receivers [total] int64.  One wavefront per sender row sweeps the N receivers of its own graph in
+ * chunks of 64: B*N*N/64 chunk iterations, not (B*N)^2/64; sender rows of another type leave at once.
+ * HGN_E_INVALID: n_graphs < 1, nodes_per_graph < 0, n_graphs * nodes_per_graph > 0x7ffffffe, whatever hgn_radius_edges_count
+ * refuses (d outside 1..3, ld < d, ldt < 1, radius not >= 0, null pos / node_type with rows, only one of nbr_rowptr / nbr),
+ * null outputs, workspace too small. */
+int hgn_radius_edges_batch_workspace_bytes(int64_t n_graphs, int64_t nodes_per_graph, size_t* bytes);
+int hgn_radius_edges_batch_count(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                 int64_t n_graphs, int64_t nodes_per_graph, float radius, int sender_type,
+                                 int receiver_type, const int32_t* nbr_rowptr, const int32_t* nbr,
+                                 int32_t* offsets /*[B*N+1]*/, int32_t* graph_offsets /*[B+1], nullable*/,
+                                 int64_t* total /*host*/, void* workspace, size_t ws_bytes, void* stream);
+int hgn_radius_edges_batch_fill(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                int64_t n_graphs, int64_t nodes_per_graph, float radius, int sender_type,
+                                int receiver_type, const int32_t* nbr_rowptr, const int32_t* nbr, const int32_t* offsets,
+                                int64_t* senders, int64_t* receivers, void* stream);
 
 /* ---- balanced Forman curvature (graph_balancer/ricci.py:128-301, the two numba-CUDA kernels of SDRF) -------------
  * Dense fp32 adjacency A [N,N] (row-major, entries 0/1), A2 = A*A [N,N], d_in[i] = column sums, d_out[j] = row sums.

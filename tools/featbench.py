@@ -4,7 +4,12 @@
     or rollout loop pays per frame -- next to the CPU oracle (the reference's op sequence) on the host cores;
   * kernel-level HBM rates of the feature kernels on a batch-sized input (64 x 9 282 edges), timed with HIP events.
 
-    python tools/featbench.py [--frames 50] [--no-cpu]
+  * whole batches of frames (B = 21, the reference's batch, and B = 128, the benchmark's): the per-frame path
+    (build_graph x B + batching.batch_graphs) against build_graph_batch for the cylinder and the plate model, and for the plate
+    with the hetero connector per-frame expand_graph + batch_graphs against expand_graph_batch -- both paths in this process, on
+    the same inputs.
+
+    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only]
 Prints one JSON object.
 """
 import argparse
@@ -41,14 +46,67 @@ def ev_time(fn, n=20, warm=3):
     return a.elapsed_time(b) / n
 
 
+def wall_time(fn, n=20, warm=3):
+    """Mean wall-clock ms of ``fn`` over ``n`` repetitions, synchronised around the timed region (host work counts)."""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e3
+
+
+def batched_builds():
+    """Per-frame path against the batched calls, cylinder and plate, B = 21 and 128 (ms per batch)."""
+    from hgn_amd import batching, synthetic, system_model
+    out = {}
+    shared = ('cells', 'mesh_pos')
+    cases = (('cylinder', system_model.CylinderModel, lambda i: synthetic.cylinder_frame(seed=i)),
+             ('plate', system_model.PlateModel, lambda i: synthetic.plate_frame(seed=i)))
+    for kind, cls, make in cases:
+        host = [make(i) for i in range(8)]
+        common = {k: host[0][k].cuda() for k in shared}
+        dev = [{k: (common[k] if k in shared else v.cuda()) for k, v in f.items()} for f in host]
+        for B in (21, 128):
+            frames = [dev[i % 8] for i in range(B)]
+            stacked = {k: (common[k] if k in shared else torch.stack([f[k] for f in frames])) for k in dev[0]}
+            model = cls(params('none', 16))
+            row = {'nodes per frame': int(host[0]['node_type'].shape[0]),
+                   'build_graph x B + batch_graphs ms': wall_time(
+                       lambda: batching.batch_graphs([model.build_graph(f, True) for f in frames])),
+                   'build_graph_batch ms': wall_time(lambda: model.build_graph_batch(stacked, True))}
+            if kind == 'plate':
+                g = model.build_graph_batch(stacked, True)
+                row['world edges in the batch'] = int(g.edge_sets[1].senders.shape[0])
+                remote = cls(params('hetero', 8))
+                remote.expand_graph(remote.build_graph(frames[0], True), 0, 10 ** 9, True)     # clustering: once, not timed
+                graphs = [remote.build_graph(f, True) for f in frames]
+                union = remote.build_graph_batch(stacked, True)
+                row['hetero K=8: expand_graph x B + batch_graphs ms'] = wall_time(
+                    lambda: batching.batch_graphs([remote.expand_graph(x, 1, 10 ** 9, True) for x in graphs]))
+                row['hetero K=8: expand_graph_batch ms'] = wall_time(lambda: remote.expand_graph_batch(union, B, 1, 10 ** 9, True))
+                row['hetero K=8: build + expand per frame + batch_graphs ms'] = wall_time(
+                    lambda: batching.batch_graphs([remote.expand_graph(remote.build_graph(f, True), 1, 10 ** 9, True) for f in frames]))
+                row['hetero K=8: build_graph_batch + expand_graph_batch ms'] = wall_time(
+                    lambda: remote.expand_graph_batch(remote.build_graph_batch(stacked, True), B, 1, 10 ** 9, True))
+            out[f'{kind} B={B}'] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=50)
     ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--batched-only', action='store_true', help='only the per-frame against batched build / expand comparison')
     a = ap.parse_args()
     from hgn_amd import features, synthetic, system_model
     from hgn_amd.normalizer import Normalizer
     res = {}
+    if a.batched_only:
+        print(json.dumps({'batched builds': batched_builds()}))
+        return
     frames = [synthetic.flag_frame(seed=i, nx=40, ny=40) for i in range(4)]
     cells = frames[0]['cells'].cuda()
     dev_frames = [{k: (cells if k == 'cells' else v.cuda()) for k, v in f.items()} for f in frames]
@@ -109,6 +167,8 @@ def main():
         features.cells_to_edges(big)
     torch.cuda.synchronize()
     res['cells_to_edges (64 meshes, 194 688 cells) ms'] = (time.perf_counter() - t0) / 5 * 1e3
+
+    res['batched builds'] = batched_builds()
 
     if not a.no_cpu:
         from bench import cpu_baseline_features          # the oracle is timed by bench.py's cpu_baseline code only
