@@ -187,6 +187,39 @@ __global__ void lincomb3_kernel(const float* __restrict__ a, float ca, const flo
   out[i] = v;
 }
 
+// One rollout step's state update, flat over [rows, F]: the expressions of normalize_kernel (inverse) and lincomb3_kernel in their
+// order, then the selection torch.where makes.  The two statistics of a column are formed per thread (three loads) instead of
+// once per block: same operations on the same values, same bits, no LDS.
+__global__ void rollout_advance_kernel(const float* __restrict__ net_out, long ld_out, int F, const float* __restrict__ acc_sum,
+                                       const float* __restrict__ acc_sumsq, const float* __restrict__ acc_count, float eps,
+                                       const float* __restrict__ cur, long ld_cur, int d, float ca,
+                                       const float* __restrict__ prev, long ld_prev, float cp,
+                                       const int64_t* __restrict__ node_type, long ldt, unsigned free_mask,
+                                       const float* __restrict__ fallback, long ld_fb, long rows, float* __restrict__ next,
+                                       long ld_next, float* __restrict__ rec, long ld_rec, int rec_before,
+                                       float* __restrict__ prev_out, long ld_po, float* __restrict__ inv, long ld_inv,
+                                       int inv_from) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * F) return;
+  const long r = i / F;
+  const int c = (int)(i - r * F);
+  const float safe = fmaxf(*acc_count, 1.f);
+  const float m = acc_sum[c] / safe;
+  const float s = fmaxf(sqrtf(fabsf(acc_sumsq[c] / safe - m * m)), eps);
+  const float x = net_out[r * ld_out + c] * s + m;                 // Normalizer.inverse
+  if (inv && c >= inv_from) inv[r * ld_inv + (c - inv_from)] = x;
+  if (c >= d) return;                                              // a column that is not integrated (cylinder: pressure)
+  const float q = cur[r * ld_cur + c];
+  float v = ca * q + 1.f * x;                                      // lincomb3 with cb = 1
+  if (prev) v = v + cp * prev[r * ld_prev + c];
+  const int64_t t = node_type[r * ldt];
+  const bool is_free = t >= 0 && t < 32 && ((free_mask >> (unsigned)t) & 1u);
+  const float nx = is_free ? v : (fallback ? fallback[r * ld_fb + c] : q);
+  next[r * ld_next + c] = nx;
+  if (rec) rec[r * ld_rec + c] = rec_before ? q : nx;
+  if (prev_out) prev_out[r * ld_po + c] = q;
+}
+
 // ----------------------------------------------------------------------------------------------------------
 // world edges by radius: one wavefront per sender row, receivers in chunks of 64 (ballot keeps ascending order)
 // ----------------------------------------------------------------------------------------------------------
@@ -676,6 +709,33 @@ extern "C" int hgn_lincomb3(const float* a, float ca, const float* b, float cb, 
   hipLaunchKernelGGL(lincomb3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, ca, b, cb, c, cc, (long)n,
                      out);
   return hgn_check_launch("hgn_lincomb3");
+}
+
+extern "C" int hgn_rollout_advance(const float* net_out, int64_t ld_out, int out_cols, int F, const float* acc_sum,
+                                   const float* acc_sumsq, const float* acc_count, float eps, const float* cur, int64_t ld_cur,
+                                   int d, float ca, const float* prev, int64_t ld_prev, float cp, const int64_t* node_type,
+                                   int64_t ldt, uint32_t free_mask, const float* fallback, int64_t ld_fb, int64_t rows,
+                                   float* next, int64_t ld_next, float* rec, int64_t ld_rec, int rec_before, float* prev_out,
+                                   int64_t ld_po, float* inv, int64_t ld_inv, int inv_from, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || !acc_sum || !acc_sumsq || !acc_count)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance: null pointer or bad width");
+  if (out_cols != F)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance: the network output's column count does not match the normaliser width");
+  if (rows < 0 || rows > 0x7fffffff || d < 1 || d > F || inv_from < 0 || inv_from > F)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance: bad sizes (0 <= rows < 2^31, 1 <= d <= F, 0 <= inv_from <= F)");
+  if (ld_out < F || ld_cur < d || ld_next < d || ldt < 1 || (prev && ld_prev < d) || (fallback && ld_fb < d) ||
+      (rec && ld_rec < d) || (prev_out && ld_po < d) || (inv && ld_inv < F - inv_from) || (inv && ld_inv < 1))
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance: bad widths / strides (a row stride is zero or smaller than its row)");
+  if (rows == 0) return HGN_OK;
+  if (!net_out || !cur || !node_type || !next) return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  const int64_t n = rows * F;
+  hipLaunchKernelGGL(rollout_advance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, net_out, (long)ld_out, F,
+                     acc_sum, acc_sumsq, acc_count, eps, cur, (long)ld_cur, d, ca, prev, (long)ld_prev, cp, node_type, (long)ldt,
+                     (unsigned)free_mask, fallback, (long)ld_fb, (long)rows, next, (long)ld_next, rec, (long)ld_rec, rec_before,
+                     prev_out, (long)ld_po, inv, (long)ld_inv, inv_from);
+  return hgn_check_launch("hgn_rollout_advance");
 }
 
 extern "C" int hgn_radius_edges_workspace_bytes(int64_t N, size_t* bytes) {

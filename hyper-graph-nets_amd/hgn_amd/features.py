@@ -340,6 +340,71 @@ def lincomb3(a: torch.Tensor, ca: float, b: torch.Tensor, cb: float, c=None, cc:
     return out
 
 
+def _out_rows(t: torch.Tensor, rows: int, width: int, what: str) -> torch.Tensor:
+    """An output of rollout_advance is written in place: fp32 [rows, width] on the device with unit-stride rows, or an error (a
+    copy would swallow the result)."""
+    if (t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, width) or not t.is_cuda
+            or (width > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < width)):
+        raise ValueError(f'rollout_advance: {what} must be a float32 device tensor [{rows}, {width}] with unit-stride rows')
+    return t
+
+
+def rollout_advance(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int, ca: float, prev, cp: float,
+                    node_type: torch.Tensor, free_types, fallback, next_out: torch.Tensor, rec=None, rec_before: bool = False,
+                    prev_out=None, inv_out=None, inv_from: int = 0) -> torch.Tensor:
+    """One rollout step's state update in one launch (hgn_rollout_advance; flag.py:169-180,243, cylinder.py:155-165,
+    plate.py:246-257,328): ``normalizer.inverse(net_out)``, the integration ``ca*cur + out[:, :d] + cp*prev`` (``prev`` may be
+    None), and per row the choice between the integrated value (node types listed in ``free_types``) and ``fallback`` (None: ``cur``).
+    Bit-identical to Normalizer.inverse -> lincomb3 -> torch.where.  Written in place: ``next_out`` [rows, d]; ``rec`` (the slice of
+    the recorded trajectory: the state before the step if ``rec_before``, else the new one); ``prev_out`` (receives ``cur``);
+    ``inv_out`` [rows, F - inv_from] (the inverse-normalised columns from ``inv_from`` on).  Outputs may be column slices of wider
+    slabs; they must not overlap the inputs.  -> ``next_out``."""
+    _lib.require_gpu(net_out)
+    dev = net_out.device
+    x = _f32_rows(net_out)
+    rows, cols = x.shape
+    F = normalizer._acc_sum.numel()
+    d = int(d)
+    cur = _f32_rows(cur.to(dev))
+    if cur.shape[0] != rows or cur.shape[1] != d:
+        raise ValueError(f'rollout_advance: cur must be [{rows}, {d}]')
+    if prev is not None:
+        prev = _f32_rows(prev.to(dev))
+        if prev.shape != cur.shape:
+            raise ValueError('rollout_advance: cur / prev shape mismatch')
+    if fallback is not None:
+        fallback = _f32_rows(fallback.to(dev))
+        if fallback.shape != cur.shape:
+            raise ValueError('rollout_advance: cur / fallback shape mismatch')
+    nt = node_type.to(device=dev, dtype=torch.int64)
+    if nt.dim() == 2:
+        nt = nt[:, 0]
+    if nt.shape[0] != rows:
+        raise ValueError(f'rollout_advance: {nt.shape[0]} node types for {rows} rows')
+    ldt = nt.stride(0) if rows > 1 else 1
+    free_mask = 0
+    for t in free_types:
+        if not 0 <= int(t) < 32:
+            raise ValueError('rollout_advance: free node types must lie in [0, 32)')
+        free_mask |= 1 << int(t)
+    _out_rows(next_out, rows, d, 'next_out')
+    if rec is not None:
+        _out_rows(rec, rows, d, 'rec')
+    if prev_out is not None:
+        _out_rows(prev_out, rows, d, 'prev_out')
+    if inv_out is not None:
+        _out_rows(inv_out, rows, F - int(inv_from), 'inv_out')
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ld = lambda t: _ld(t) if t is not None else 0
+    _lib.check(_lib.lib().hgn_rollout_advance(
+        x.data_ptr(), _ld(x), cols, F, normalizer._acc_sum.data_ptr(), normalizer._acc_sum_squared.data_ptr(),
+        normalizer._acc_count.data_ptr(), float(normalizer._eps), cur.data_ptr(), _ld(cur), d, float(ca), ptr(prev), ld(prev),
+        float(cp), nt.data_ptr(), ldt, free_mask, ptr(fallback), ld(fallback), rows, next_out.data_ptr(), _ld(next_out),
+        ptr(rec), ld(rec), 1 if rec_before else 0, ptr(prev_out), ld(prev_out), ptr(inv_out), ld(inv_out), int(inv_from),
+        _lib.stream_ptr()), 'hgn_rollout_advance')
+    return next_out
+
+
 def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, sender_type: int, receiver_type: int,
                  nbr_rowptr=None, nbr=None):
     """plate.py:84-110: directed pairs closer than ``radius`` with the given endpoint types that are not mesh

@@ -225,12 +225,66 @@ class AbstractSystemModel(nn.Module):
         """[T, N, D] x 2 -> [T]: squared error averaged over components, then over nodes (the reference's two nested means)."""
         return ((truth - predicted) ** 2).mean(dim=-1).mean(dim=-1).detach()
 
+    # ---- lock-step evaluation: W windows of one mesh advance as one batch of W frames -------------------------------
+    nstep_batch = None      # None: n_step_computation rolls the windows out one by one (the reference's loop); M > 0: M at a time
+
+    @staticmethod
+    def _window_start(windows: Dict[str, Tensor], name: str) -> Tensor:
+        """Frame 0 of every window of a [W, T, N, .] series -> [W, N, .] on the device, in memory of its own (the windows may be
+        overlapping views of one trajectory)."""
+        return windows[name][:, 0].to(device, copy=True).contiguous()    # a copy: the state buffers are written, the trajectory is not
+
+    @staticmethod
+    def _shared_mesh(windows: Dict[str, Tensor]) -> Tuple[Tensor, Tensor]:
+        """(cells [F, v], mesh_pos [N, .] or [W, N, .]) of a set of windows: `cells` given once, or with leading window / frame
+        dimensions (the first one is taken: one mesh for all windows); `mesh_pos` given once, or as a [W, T, N, .] series whose
+        frame 0 is used, as `rollout` uses frame 0 of its trajectory."""
+        cells, mesh_pos = windows['cells'], windows['mesh_pos']
+        while cells.dim() > 2:
+            cells = cells[0]
+        return cells, (mesh_pos[:, 0] if mesh_pos.dim() == 4 else mesh_pos).to(device)
+
+    def _batch_errors(self, windows: Dict[str, Tensor], name: str, slab: Tensor) -> Tensor:
+        """Per-step errors [W, steps] of a recorded [steps, W, N, d] slab against the windows' own frames, in one call."""
+        truth = windows[name][:, :slab.shape[0]].to(device).transpose(0, 1)
+        return self._per_step_mse(truth, slab).transpose(0, 1)
+
+    @staticmethod
+    def window_views(trajectory: Dict[str, Tensor], n_step: int, frames: int) -> Dict[str, Tensor]:
+        """All frames - n_step sliding windows of n_step + 1 frames as strided views of the trajectory's series ([T, ...] ->
+        [W, n_step + 1, ...], window w = frames w .. w + n_step): what n_step_computation's loop slices one window at a time,
+        without a copy per window."""
+        horizon, count = n_step + 1, frames - n_step
+        views = {}
+        for name, series in trajectory.items():
+            if series.shape[0] < frames:
+                raise ValueError(f'window_views: series {name!r} has {series.shape[0]} frames, {frames} asked for')
+            views[name] = series.as_strided((count, horizon) + tuple(series.shape[1:]), (series.stride(0),) + tuple(series.stride()))
+        return views
+
     @torch.no_grad()
     def n_step_computation(self, trajectory: Dict[str, Tensor], n_step: int, num_timesteps=None) -> Tuple[Tensor, Tensor]:
         """Sliding n-step rollouts (flag.py:248-260): every window of n_step + 1 consecutive frames is rolled out from its
-        first frame; returns (mean over windows of the window's mean error, mean over windows of its final-step error)."""
+        first frame; returns (mean over windows of the window's mean error, mean over windows of its final-step error).
+        With `self.nstep_batch = M > 0` (not in the reference) the windows advance in lock step, at most M at a time, through
+        `rollout_batch`: one union graph of M frames per step instead of M graphs of one frame.  The windows are strided views of
+        the trajectory, which must be one mesh throughout.  A model with a connector or a graph balancer ignores `nstep_batch` and
+        takes the loop: the reference clusters (and balances) every window anew from that window's own first frame, while
+        expand_graph_batch clusters once, from the first frame of the batch."""
         horizon = n_step + 1
         frames = trajectory['cells'].shape[0] if num_timesteps is None else num_timesteps
+        batch = self.nstep_batch
+        if batch and batch > 0 and frames > n_step and not (self._rmp or self._balancer):
+            views = self.window_views({name: series.to(device) for name, series in trajectory.items()}, n_step, frames)
+            cells = views.pop('cells')[0, 0]
+            chunks = []
+            for first in range(0, frames - n_step, int(batch)):
+                windows = {name: series[first:first + int(batch)] for name, series in views.items()}
+                windows['cells'] = cells
+                chunks.append(self.rollout_batch(windows, horizon)[1])
+            errors = torch.cat(chunks).cpu()
+            window_means, window_finals = [e.mean() for e in errors], [e[-1] for e in errors]
+            return torch.stack(window_means).mean(), torch.stack(window_finals).mean()
         window_means, window_finals = [], []
         for start in range(frames - n_step):
             window = {name: series[start:start + horizon] for name, series in trajectory.items()}
@@ -348,6 +402,35 @@ class FlagModel(AbstractSystemModel):
                 'pred_pos': predictions}, errors
 
     @torch.no_grad()
+    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int) -> Tuple[Dict[str, Tensor], Tensor]:
+        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `world_pos`, `prev|world_pos`, `node_type` are
+        [W, T, N, .] (window w may be a view of a longer trajectory); `cells` and a `mesh_pos` shared by all windows are given once.
+        The W windows advance in lock step: every step is one build_graph_batch over the W current states (is_training=False),
+        expand_graph_batch, the network, and one features.rollout_advance launch that integrates, keeps the HANDLE nodes and writes
+        the state BEFORE the step into its slice of the recorded [steps, W, N, 3] slab.  -> what `rollout` returns per window:
+        `pred_pos` [W, steps, N, 3], errors [W, steps].  As in `rollout`, the node-dynamic normaliser accumulates on every build
+        (flag.py:115), here once per step with the statistics of the W frames."""
+        if num_steps is None:
+            num_steps = windows['world_pos'].shape[1]
+        cells, mesh_pos = self._shared_mesh(windows)
+        cur, prev = self._window_start(windows, 'world_pos'), self._window_start(windows, 'prev|world_pos')
+        node_type = self._window_start(windows, 'node_type').to(torch.int64)
+        W, N = cur.shape[0], cur.shape[1]
+        slab = torch.empty(num_steps, W, N, 3, dtype=torch.float32, device=cur.device)
+        nxt, prev_nxt = torch.empty_like(cur), torch.empty_like(prev)
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
+        for step in range(num_steps):
+            frame['world_pos'], frame['prev|world_pos'] = cur, prev
+            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, 399, is_training=False)
+            features.rollout_advance(self(graph), self._output_normalizer, cur.view(W * N, 3), 3, 2.0, prev.view(W * N, 3), -1.0,
+                                     node_type.view(W * N, -1), (NodeType.NORMAL.value,), None, nxt.view(W * N, 3),
+                                     rec=slab[step].view(W * N, 3), rec_before=True, prev_out=prev_nxt.view(W * N, 3))
+            cur, nxt, prev, prev_nxt = nxt, cur, prev_nxt, prev
+        self._visualized = False
+        return {'faces': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'gt_pos': windows['world_pos'],
+                'pred_pos': slab.transpose(0, 1)}, self._batch_errors(windows, 'world_pos', slab)
+
+    @torch.no_grad()
     def _step_fn(self, initial_state, prev_pos, cur_pos, trajectory, mask, step):
         """flag.py:227-246."""
         frame = dict(initial_state)
@@ -451,6 +534,35 @@ class CylinderModel(AbstractSystemModel):
         errors = self._per_step_mse(trajectory['velocity'][:num_steps].to(device), pred_velocity)
         return {'faces': trajectory['cells'], 'mesh_pos': trajectory['mesh_pos'], 'gt_velocity': trajectory['velocity'],
                 'gt_pressure': trajectory['pressure'], 'pred_pressure': torch.stack(pressures), 'pred_velocity': pred_velocity}, errors
+
+    @torch.no_grad()
+    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int):
+        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `velocity`, `node_type` are [W, T, N, .]; `cells` and
+        a `mesh_pos` shared by all windows are given once.  Like `rollout`, it runs the whole window length T whatever `num_steps`
+        says (cylinder.py:178).  Every step is one build_graph_batch over the W current states (is_training=False),
+        expand_graph_batch, the network, and one features.rollout_advance launch that integrates the NORMAL and OUTFLOW nodes and
+        writes the state AFTER the step and the predicted pressure into their slices of the recorded [T, W, N, .] slabs.
+        -> what `rollout` returns per window: `pred_velocity` [W, T, N, 2], `pred_pressure` [W, T, N, 1], errors [W, T]."""
+        num_steps = windows['velocity'].shape[1]
+        cells, mesh_pos = self._shared_mesh(windows)
+        velocity = self._window_start(windows, 'velocity')
+        node_type = self._window_start(windows, 'node_type').to(torch.int64)
+        W, N = velocity.shape[0], velocity.shape[1]
+        slab = torch.empty(num_steps, W, N, 2, dtype=torch.float32, device=velocity.device)
+        pressures = torch.empty(num_steps, W, N, 1, dtype=torch.float32, device=velocity.device)
+        nxt = torch.empty_like(velocity)
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
+        for step in range(num_steps):
+            frame['velocity'] = velocity
+            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, 598, is_training=False)
+            features.rollout_advance(self(graph), self._output_normalizer, velocity.view(W * N, 2), 2, 1.0, None, 0.0,
+                                     node_type.view(W * N, -1), (NodeType.NORMAL.value, NodeType.OUTFLOW.value), None,
+                                     nxt.view(W * N, 2), rec=slab[step].view(W * N, 2), inv_out=pressures[step].view(W * N, 1),
+                                     inv_from=2)
+            velocity, nxt = nxt, velocity
+        return {'faces': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'gt_velocity': windows['velocity'],
+                'gt_pressure': windows.get('pressure'), 'pred_pressure': pressures.transpose(0, 1),
+                'pred_velocity': slab.transpose(0, 1)}, self._batch_errors(windows, 'velocity', slab)
 
     @torch.no_grad()
     def _step_fn(self, initial_state, velocity, pressure, trajectory, pressure_trajectory, step, mask):
@@ -613,6 +725,40 @@ class PlateModel(AbstractSystemModel):
         return {'faces': triangles, 'mesh_pos': trajectory['mesh_pos'],
                 'mask': torch.eq(start['node_type'][:, 0], NodeType.OBSTACLE.value), 'gt_pos': trajectory['world_pos'],
                 'pred_pos': pred_pos, 'cur_positions': torch.stack(positions), 'cur_velocities': torch.stack(velocities)}, errors
+
+    @torch.no_grad()
+    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int):
+        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `world_pos`, `target|world_pos`, `node_type` are
+        [W, T, N, .]; `cells` and a `mesh_pos` shared by all windows are given once.  Every step is one build_graph_batch over the W
+        current states (is_training=False; one radius query for all windows), expand_graph_batch, the network, and one
+        features.rollout_advance launch that moves the NORMAL nodes by the predicted velocity, puts the scripted nodes on
+        `target|world_pos[w, t]` and writes the new position, the position before the step and the velocity into their slices of the
+        recorded [steps, W, N, 3] slabs.  -> what `rollout` returns per window: `pred_pos`, `cur_positions`, `cur_velocities`
+        [W, steps, N, 3], `mask` [W, N], errors [W, steps]."""
+        if num_steps is None:
+            num_steps = windows['world_pos'].shape[1]
+        cells, mesh_pos = self._shared_mesh(windows)
+        position = self._window_start(windows, 'world_pos')
+        node_type = self._window_start(windows, 'node_type').to(torch.int64)
+        W, N = position.shape[0], position.shape[1]
+        scripted = windows['target|world_pos'][:, :num_steps].to(device).transpose(0, 1).contiguous()       # [steps, W, N, 3], once
+        slab, before, velocities = (torch.empty(num_steps, W, N, 3, dtype=torch.float32, device=position.device) for _ in range(3))
+        nxt = torch.empty_like(position)
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
+        for step in range(num_steps):
+            frame['world_pos'], frame['target|world_pos'] = position, scripted[step]
+            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, num_steps, is_training=False)
+            features.rollout_advance(self(graph), self._output_normalizer, position.view(W * N, 3), 3, 1.0, None, 0.0,
+                                     node_type.view(W * N, -1), (NodeType.NORMAL.value,), scripted[step].view(W * N, 3),
+                                     nxt.view(W * N, 3), rec=slab[step].view(W * N, 3), prev_out=before[step].view(W * N, 3),
+                                     inv_out=velocities[step].view(W * N, 3), inv_from=0)
+            position, nxt = nxt, position
+        cells_all = windows['cells']
+        triangles = torch.cat((cells_all[..., 0:3], cells_all[..., [2, 3, 0]]), dim=-2)                 # plate.py:289-297
+        return {'faces': triangles, 'mesh_pos': windows['mesh_pos'],
+                'mask': torch.eq(node_type[:, :, 0], NodeType.OBSTACLE.value), 'gt_pos': windows['world_pos'],
+                'pred_pos': slab.transpose(0, 1), 'cur_positions': before.transpose(0, 1),
+                'cur_velocities': velocities.transpose(0, 1)}, self._batch_errors(windows, 'world_pos', slab)
 
     @torch.no_grad()
     def _step_fn(self, initial_state, cur_pos, trajectory, cur_positions, cur_velocities, target_world_pos, step, mask,

@@ -15,6 +15,8 @@
  *                                    world edges of a batch of frames, one query -> hgn_radius_edges_batch_count/_fill
  *   graph_balancer/ricci.py:128-301  balanced Forman curvature kernels (SDRF)   -> hgn_forman_curvature/_post_delta
  *   model/flag.py:178,188, cylinder.py:163,171  target / integrator arithmetic   -> hgn_lincomb3
+ *   model/flag.py:169-180,243, cylinder.py:155-165, plate.py:246-257,328
+ *                                    one rollout step's state update            -> hgn_rollout_advance
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
  *                                                                              hgn_normalizer_update, hgn_normalize
  */
@@ -174,6 +176,34 @@ int hgn_forman_post_delta(const float* A, const float* A2, float d_in_x, float d
  * come out bit-identical to the reference's left-to-right fp32 evaluation.  n = number of elements (contiguous). */
 int hgn_lincomb3(const float* a, float ca, const float* b, float cb, const float* c, float cc, int64_t n, float* out,
                  void* stream);
+
+/* ---- one rollout step's state update (flag.py:169-180,243, cylinder.py:155-165, plate.py:246-257,328) ----------
+ * What Normalizer.inverse -> hgn_lincomb3 -> torch.where -> append do in a rollout step, in ONE launch and with the same
+ * device expressions in the same order (hgn_normalize with inverse = 1, then hgn_lincomb3 with cb = 1): equal bits.
+ * Per row r of net_out [rows, ld_out] (the network output, normalised; out_cols columns, which must equal the normaliser
+ * width F) and per column c:
+ *   x     = net_out[r,c] * max(std[c], eps) + mean[c]                    (statistics as in hgn_normalize)
+ *   c >= inv_from:  inv[r, c - inv_from] = x                           (inv nullable: cylinder's pressure with inv_from = d,
+ *                                                                         plate's velocity with inv_from = 0)
+ *   c <  d:         v    = (ca * cur[r,c] + x) + cp * prev[r,c]          (prev nullable: the last term is left out)
+ *                   next[r,c] = v  if bit node_type[r] of free_mask is set  (types outside [0, 32) are never free)
+ *                               else fallback[r,c]                       (fallback nullable: cur[r,c]; plate: the scripted target)
+ *                   rec[r,c]      = rec_before ? cur[r,c] : next[r,c]    (rec nullable: the slice of the recorded trajectory;
+ *                                                                         flag records the state BEFORE the step)
+ *                   prev_out[r,c] = cur[r,c]                             (prev_out nullable: flag's next prev|world_pos,
+ *                                                                         plate's cur_positions)
+ * Every matrix has its own row stride (>= its row width), so an output may be a column slice of a wider slab.  Outputs must
+ * not overlap inputs or each other.  node_type int64 with element stride ldt.  One thread per element of net_out, vector
+ * loads and stores only: no atomics, no LDS, rows independent, equal bits on every run.
+ * HGN_E_INVALID: null statistics, F outside 1..HGN_MAX_FEATURE_WIDTH, out_cols != F, rows outside [0, 2^31), d outside 1..F,
+ * inv_from outside 0..F, a row stride that is zero or smaller than its row, null net_out / cur / node_type / next with
+ * rows > 0. */
+int hgn_rollout_advance(const float* net_out, int64_t ld_out, int out_cols, int F, const float* acc_sum,
+                        const float* acc_sumsq, const float* acc_count, float eps, const float* cur, int64_t ld_cur, int d,
+                        float ca, const float* prev, int64_t ld_prev, float cp, const int64_t* node_type, int64_t ldt,
+                        uint32_t free_mask, const float* fallback, int64_t ld_fb, int64_t rows, float* next, int64_t ld_next,
+                        float* rec, int64_t ld_rec, int rec_before, float* prev_out, int64_t ld_po, float* inv,
+                        int64_t ld_inv, int inv_from, void* stream);
 
 #ifdef __cplusplus
 }
