@@ -501,6 +501,11 @@ class MeshGraphNet(nn.Module):
         process default.  Other models of the process are not affected."""
         self._hgn_ctx.set_matmul_precision(mode)
 
+    def set_fp32_mfma(self, on) -> None:
+        """This model's launches on the plain fp32-MFMA kernels (True) or the split-product ones (False); None = follow the process
+        default (HGN_FP32_MFMA at import).  Other models of the process are not affected."""
+        self._hgn_ctx.fp32_mfma = None if on is None else bool(on)
+
     def forward(self, graph: MultiGraph) -> Tensor:
         if self._latent_size != ops.LAT or self._num_layers != 2:
             raise HgnError('the HIP path implements latent_size=128, num_layers=2 (hard-coded by the reference models: '

@@ -1315,9 +1315,8 @@ def test_split_products_cover_the_fp32_range(mode):
 
 def test_split_bf16_products_are_fp32_accurate():
     """The default kernels evaluate each fp32 product as six bf16 MFMAs on 3-way bf16 splits (csrc/mlp6.hip): against fp64 they
-    must be as accurate as the plain fp32-MFMA kernels (HGN_FP32_MFMA=1) on the same inputs -- forward, data gradients and
+    must be as accurate as the plain fp32-MFMA kernels (ops.Context(fp32_mfma=True)) on the same inputs -- forward, data gradients and
     weight gradients of an edge block and of a two-source node MLP."""
-    import os
     from hgn_amd import ops, topology, modules
     import hgn_amd
     g = synth.grid_graph(seed=3, nx=20, ny=20)
@@ -1331,8 +1330,6 @@ def test_split_bf16_products_are_fp32_accurate():
     blk = m.processor.graphnet_blocks[0]
     we = modules.weights_of(blk.edge_models['mesh_edges'], 384)
     wn = modules.weights_of(blk.node_model_cross, 256)
-    h0 = torch.randn(N, 128, generator=torch.Generator().manual_seed(1)).cuda()
-    e0 = torch.randn(E, 128, generator=torch.Generator().manual_seed(2)).cuda()
 
     def run():
         h = h0.clone().requires_grad_(True); e = e0.clone().requires_grad_(True)
@@ -1360,13 +1357,25 @@ def test_split_bf16_products_are_fp32_accurate():
         hn = h + mlp(torch.cat([h, agg], 1), 'node_model_cross')
         (hn.square().sum() + y.square().sum()).backward()
         return [y.detach(), hn.detach(), h.grad, e.grad] + [p.grad for p in ps]
-    r64 = ref64()
+    # The inputs: the first seed pair (1, 2), (3, 4), ... whose fp64 run keeps every ReLU input farther than 3e-7 from zero (the criterion
+    # of test_flag_L15_sum_vs_oracle_fp64).  With (1, 2) one second-layer input of the edge MLP is 3.4e-8 in fp64, below the rounding of
+    # any fp32 evaluation: the split kernels gate that unit the other way than fp64 and the plain ones do not -- 5e-3 in dh / de and the
+    # edge MLP's first two layers from ONE gate, which says nothing about the products (tests/helpers.py: gate transfer).
+    for s0 in range(1, 41, 2):
+        h0 = torch.randn(N, 128, generator=torch.Generator().manual_seed(s0)).cuda()
+        e0 = torch.randn(E, 128, generator=torch.Generator().manual_seed(s0 + 1)).cuda()
+        with _KinkMargin() as km:
+            r64 = ref64()
+        if km.worst > 3e-7:
+            break
+    assert km.worst > 3e-7, km.worst
+    H._REPORT.append({'test': 'test_split_bf16_products_are_fp32_accurate', 'what': 'instance selection', 'first_seed_tried': 1, 'seed_used': s0,
+                      'seeds_rejected': (s0 - 1) // 2, 'criterion': 'smallest |ReLU input| of the fp64 run > 3e-7', 'margin_of_seed_used': km.worst})
     split = run()
-    os.environ['HGN_FP32_MFMA'] = '1'                      # read by the library at every launch
-    try:
+    # (the environment variable of that name is read once, at import, into the process default; a Context carries the flag per call)
+    with ops.using(ops.Context(fp32_mfma=True)):
         plain = run()
-    finally:
-        del os.environ['HGN_FP32_MFMA']
+    assert any(not torch.equal(a, b) for a, b in zip(split, plain))      # other kernels ran: other products, other summation order
     for a, b, c in zip(split, plain, r64):
         e6, e32 = H.rel_err(a, c), H.rel_err(b, c)
         assert e6 <= max(1.5 * e32, 2e-6), (e6, e32)

@@ -663,6 +663,14 @@ def test_two_contexts_with_different_precisions_from_two_threads_through_the_abi
     assert m1._hgn_ctx is not m2._hgn_ctx and m1._hgn_ctx.wq is not m2._hgn_ctx.wq
     m2.set_matmul_precision('bf16')
     assert (m1._hgn_ctx.products(), m2._hgn_ctx.products()) == (3, 1)
+    # ... and the plain fp32-MFMA kernels per model: the flag of that model's structs only; None follows the process default again
+    m1.set_fp32_mfma(True)
+    assert m1._hgn_ctx.fp32_only() and not m2._hgn_ctx.fp32_only() and not ops.default_context().fp32_only()
+    a = _lib.MlpFwd()
+    m1._hgn_ctx.stamp(a)
+    assert a.flags & _lib.F_FP32_MFMA
+    m1.set_fp32_mfma(None)
+    assert m1._hgn_ctx.fp32_only() == ops.default_context().fp32_only()
 
 
 def test_topology_parts_of_a_hierarchical_graph():
