@@ -220,6 +220,36 @@ __global__ void rollout_advance_kernel(const float* __restrict__ net_out, long l
   if (prev_out) prev_out[r * ld_po + c] = q;
 }
 
+// Backward of rollout_advance_kernel, flat over [rows, F] like the forward: the scale of a column is formed per thread with the
+// forward's expressions, every output element is written exactly once (zeros included), no LDS, no atomics.
+// g = d_next[r,c] (0 when absent or c >= d), h = d_inv[r, c - inv_from] (0 when absent or c < inv_from).
+__global__ void rollout_advance_bwd_kernel(const float* __restrict__ d_next, long ld_dn, const float* __restrict__ d_inv,
+                                           long ld_di, int inv_from, int F, const float* __restrict__ acc_sum,
+                                           const float* __restrict__ acc_sumsq, const float* __restrict__ acc_count, float eps,
+                                           int d, float ca, float cp, const int64_t* __restrict__ node_type, long ldt,
+                                           unsigned free_mask, int has_fallback, long rows, float* __restrict__ d_net,
+                                           long ld_net, float* __restrict__ d_cur, long ld_dc, float* __restrict__ d_prev,
+                                           long ld_dp, float* __restrict__ d_fb, long ld_df) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * F) return;
+  const long r = i / F;
+  const int c = (int)(i - r * F);
+  const float g = (d_next && c < d) ? d_next[r * ld_dn + c] : 0.f;
+  const float h = (d_inv && c >= inv_from) ? d_inv[r * ld_di + (c - inv_from)] : 0.f;
+  const int64_t t = node_type[r * ldt];
+  const bool is_free = t >= 0 && t < 32 && ((free_mask >> (unsigned)t) & 1u);
+  if (d_net) {
+    const float safe = fmaxf(*acc_count, 1.f);
+    const float m = acc_sum[c] / safe;
+    const float s = fmaxf(sqrtf(fabsf(acc_sumsq[c] / safe - m * m)), eps);   // the forward's s_c
+    d_net[r * ld_net + c] = s * (is_free ? g + h : h);
+  }
+  if (c >= d) return;
+  if (d_cur) d_cur[r * ld_dc + c] = is_free ? ca * g : (has_fallback ? 0.f : g);
+  if (d_prev) d_prev[r * ld_dp + c] = is_free ? cp * g : 0.f;
+  if (d_fb) d_fb[r * ld_df + c] = (is_free || !has_fallback) ? 0.f : g;
+}
+
 // ----------------------------------------------------------------------------------------------------------
 // world edges by radius: one wavefront per sender row, receivers in chunks of 64 (ballot keeps ascending order)
 // ----------------------------------------------------------------------------------------------------------
@@ -736,6 +766,33 @@ extern "C" int hgn_rollout_advance(const float* net_out, int64_t ld_out, int out
                      (unsigned)free_mask, fallback, (long)ld_fb, (long)rows, next, (long)ld_next, rec, (long)ld_rec, rec_before,
                      prev_out, (long)ld_po, inv, (long)ld_inv, inv_from);
   return hgn_check_launch("hgn_rollout_advance");
+}
+
+extern "C" int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, const float* d_inv, int64_t ld_dinv, int inv_from,
+                                       int F, const float* acc_sum, const float* acc_sumsq, const float* acc_count, float eps,
+                                       int d, float ca, float cp, const int64_t* node_type, int64_t ldt, uint32_t free_mask,
+                                       int has_fallback, int64_t rows, float* d_net, int64_t ld_dnet, float* d_cur,
+                                       int64_t ld_dcur, float* d_prev, int64_t ld_dprev, float* d_fallback, int64_t ld_dfb,
+                                       void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || !acc_sum || !acc_sumsq || !acc_count)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance_bwd: null pointer or bad width");
+  if (rows < 0 || rows > 0x7fffffff || d < 1 || d > F || inv_from < 0 || inv_from > F)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance_bwd: bad sizes (0 <= rows < 2^31, 1 <= d <= F, 0 <= inv_from <= F)");
+  if (ldt < 1 || (d_next && ld_dnext < d) || (d_inv && ld_dinv < F - inv_from) || (d_inv && ld_dinv < 1) ||
+      (d_net && ld_dnet < F) || (d_cur && ld_dcur < d) || (d_prev && ld_dprev < d) || (d_fallback && ld_dfb < d))
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance_bwd: bad widths / strides (a row stride is zero or smaller than its row)");
+  if (!d_net && !d_cur && !d_prev && !d_fallback)
+    return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance_bwd: no output asked for (d_net, d_cur, d_prev and d_fallback are all null)");
+  if (rows == 0) return HGN_OK;
+  if (!node_type) return hgn_fail(HGN_E_INVALID, "hgn_rollout_advance_bwd: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  const int64_t n = rows * F;
+  hipLaunchKernelGGL(rollout_advance_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_next, (long)ld_dnext,
+                     d_inv, (long)ld_dinv, inv_from, F, acc_sum, acc_sumsq, acc_count, eps, d, ca, cp, node_type, (long)ldt,
+                     (unsigned)free_mask, has_fallback, (long)rows, d_net, (long)ld_dnet, d_cur, (long)ld_dcur, d_prev,
+                     (long)ld_dprev, d_fallback, (long)ld_dfb);
+  return hgn_check_launch("hgn_rollout_advance_bwd");
 }
 
 extern "C" int hgn_radius_edges_workspace_bytes(int64_t N, size_t* bytes) {

@@ -405,6 +405,68 @@ def rollout_advance(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int
     return next_out
 
 
+def _advance_into_fresh(net_out, normalizer, cur, d, ca, prev, cp, node_type, free_types, fallback, inv_from):
+    rows, F = _f32_rows(net_out).shape[0], normalizer._acc_sum.numel()
+    nxt = torch.empty(rows, d, dtype=torch.float32, device=net_out.device)
+    inv = torch.empty(rows, F - int(inv_from), dtype=torch.float32, device=net_out.device) if inv_from is not None else None
+    rollout_advance(net_out, normalizer, cur, d, ca, prev, cp, node_type, free_types, fallback, nxt, inv_out=inv,
+                    inv_from=int(inv_from or 0))
+    return nxt, inv
+
+
+class _AdvanceStateFn(torch.autograd.Function):
+    """The statistics are constants, and later accumulations update them in place: the backward pass uses the values this forward
+    call normalised with (three tiny copies, as in _NormalizeFn)."""
+
+    @staticmethod
+    def forward(ctx, net_out, cur, prev, fallback, normalizer, d, ca, cp, node_type, free_types, inv_from):
+        ctx.set_materialize_grads(False)
+        det = lambda t: t.detach() if t is not None else None
+        nxt, inv = _advance_into_fresh(net_out.detach(), normalizer, cur.detach(), d, ca, det(prev), cp, node_type, free_types,
+                                       det(fallback), inv_from)
+        nt = node_type.to(device=net_out.device, dtype=torch.int64)
+        ctx.cfg = (float(normalizer._eps), d, ca, cp, nt[:, 0] if nt.dim() == 2 else nt, sum(1 << int(t) for t in set(free_types)),
+                   int(inv_from or 0), net_out, cur, prev, fallback)
+        ctx.save_for_backward(normalizer._acc_sum.detach().clone(), normalizer._acc_sum_squared.detach().clone(),
+                              normalizer._acc_count.detach().clone())
+        return nxt, inv
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_next, d_inv):
+        eps, d, ca, cp, nt, free_mask, inv_from, net_out, cur, prev, fallback = ctx.cfg
+        acc_sum, acc_sumsq, acc_count = ctx.saved_tensors
+        dev, F, rows = acc_sum.device, acc_sum.numel(), nt.shape[0]
+        g = _f32_rows(d_next.to(dev)) if d_next is not None else None         # an incoming gradient may have any stride
+        h = _f32_rows(d_inv.to(dev)) if d_inv is not None else None
+        want = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], prev is not None and ctx.needs_input_grad[2],
+                fallback is not None and ctx.needs_input_grad[3]]
+        outs = [torch.empty(rows, w, dtype=torch.float32, device=dev) if need else None for need, w in zip(want, (F, d, d, d))]
+        if any(want):
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            ld = lambda t: _ld(t) if t is not None else 0
+            _lib.check(_lib.lib().hgn_rollout_advance_bwd(
+                ptr(g), ld(g), ptr(h), ld(h), inv_from, F, acc_sum.data_ptr(), acc_sumsq.data_ptr(), acc_count.data_ptr(), eps, d,
+                ca, cp, nt.data_ptr(), nt.stride(0) if rows > 1 else 1, free_mask, 1 if fallback is not None else 0, rows,
+                ptr(outs[0]), ld(outs[0]), ptr(outs[1]), ld(outs[1]), ptr(outs[2]), ld(outs[2]), ptr(outs[3]), ld(outs[3]),
+                _lib.stream_ptr()), 'hgn_rollout_advance_bwd')
+        refs = (net_out, cur, prev, fallback)
+        return tuple(_like(o, r) if o is not None else None for o, r in zip(outs, refs)) + (None,) * 7
+
+
+def advance_state(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int, ca: float, prev, cp: float,
+                  node_type: torch.Tensor, free_types, fallback=None, inv_from=None):
+    """``rollout_advance`` as a function: the same one launch (hgn_rollout_advance, hence the bits of Normalizer.inverse -> lincomb3
+    -> torch.where) written into fresh tensors.  -> (next [rows, d], the inverse-normalised columns from ``inv_from`` on
+    [rows, F - inv_from], or None when ``inv_from`` is None).  Differentiable with respect to ``net_out``, ``cur``, ``prev`` and
+    ``fallback`` in one launch of its own (hgn_rollout_advance_bwd); the normaliser's statistics are constants."""
+    _lib.require_gpu(net_out)
+    d, ca, cp = int(d), float(ca), float(cp)
+    if _needs_grad(net_out, cur, prev, fallback):
+        return _AdvanceStateFn.apply(net_out, cur, prev, fallback, normalizer, d, ca, cp, node_type, tuple(free_types), inv_from)
+    return _advance_into_fresh(net_out, normalizer, cur, d, ca, prev, cp, node_type, free_types, fallback, inv_from)
+
+
 def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, sender_type: int, receiver_type: int,
                  nbr_rowptr=None, nbr=None):
     """plate.py:84-110: directed pairs closer than ``radius`` with the given endpoint types that are not mesh

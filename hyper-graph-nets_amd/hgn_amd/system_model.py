@@ -262,6 +262,69 @@ class AbstractSystemModel(nn.Module):
             views[name] = series.as_strided((count, horizon) + tuple(series.shape[1:]), (series.stride(0),) + tuple(series.stride()))
         return views
 
+    # ---- training on unrolled rollouts: the W windows advance in lock step, with autograd ---------------------------------
+    # Per model: (state series, the series that receives the old state or None, d, ca, cp, free node types, the per-step series
+    # get_target reads, the per-step series a row that is not free falls back to or None: its own state,
+    # whether build_graph_batch is differentiable with respect to the state).
+    _UNROLL = None
+
+    def unrolled_training_step(self, windows: Dict[str, Tensor], n_steps: int, through_state: bool = True,
+                               is_training: bool = True) -> Tuple[Tensor, Tensor]:
+        """Not in the reference, which trains on single steps only: the loss of an ``n_steps`` rollout unrolled under autograd, the
+        remedy for rollout drift.  ``windows`` has the layout `rollout_batch` takes -- [W, T, N, .] series with T >= n_steps,
+        `cells` and a `mesh_pos` shared by all windows given once -- and also holds the per-step series `get_target` reads
+        (`target|world_pos`; cylinder: `target|velocity` and `pressure`).  All W windows advance in lock step.  Step t builds the
+        frame of the W current states (node types and the initial state from frame 0, the targets from frame t; for the plate, frame
+        t's `target|world_pos` is also the scripted motion), forms one union graph with build_graph_batch / expand_graph_batch, runs
+        the network, takes the masked MSE against `get_target` of that frame exactly as `training_step` does, and gets the next
+        state from ONE features.advance_state launch with the constants `rollout_batch` integrates with.
+        Only step 0 sees dataset values, so with ``is_training`` only step 0 accumulates into the normalisers (the flag's
+        node-dynamic normaliser accumulates on every build, as in `rollout_batch`).
+        ``through_state=True``: the next state keeps its autograd history; gradients flow through advance_state, build_graph_batch
+        and the state terms of get_target of all later steps.  ``through_state=False`` (push-forward): the state is detached before
+        the next step, so every step's loss differentiates the parameters at that step only; this needs no differentiable graph
+        construction and therefore also works for PlateModel and for models with a connector, which refuse ``through_state=True``
+        with ``n_steps`` > 1.  A configured graph balancer raises what expand_graph_batch raises.
+        -> (loss = the mean of the per-step losses, the per-step losses detached [n_steps]).  ``n_steps`` = 1 is `training_step` on
+        the batched graph, bit for bit.
+        Out of scope: HIP-graph capture of the unrolled step; the data-parallel trainer (parallel.Trainer.step keeps its single-step
+        loss; this method returns an ordinary loss for any optimiser); activation checkpointing; meshes that differ within a batch."""
+        state_name, old_name, d, ca, cp, free_types, per_step, fallback_name, differentiable = self._UNROLL
+        n_steps = int(n_steps)
+        if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (state_name,) + tuple(per_step)):
+            raise ValueError(f'unrolled_training_step: n_steps = {n_steps} needs windows of at least that many frames (and n_steps >= 1)')
+        if through_state and n_steps > 1 and (self._rmp or not differentiable):
+            raise _lib.HgnError('unrolled_training_step: through_state=True differentiates build_graph_batch and expand_graph_batch with '
+                                'respect to the state, which PlateModel and models with a connector cannot do; pass through_state=False '
+                                '(push-forward: the state is detached between the steps)')
+        cells, mesh_pos = self._shared_mesh(windows)
+        node_type = windows['node_type'][:, 0].to(device).to(torch.int64)
+        W, N = node_type.shape[0], node_type.shape[1]
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type, state_name: windows[state_name][:, 0].to(device)}
+        if old_name is not None:
+            frame[old_name] = windows[old_name][:, 0].to(device)
+        losses = []
+        for t in range(n_steps):
+            for name in per_step:
+                frame[name] = windows[name][:, t].to(device)
+            accumulate = bool(is_training) and t == 0
+            graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate)
+            flat = self.flatten_frames(frame)
+            output = self(graph)
+            losses.append(_masked_mse(self.get_target(flat, accumulate), output, self._loss_mask(flat)))
+            if t + 1 == n_steps:
+                break
+            cur = flat[state_name]
+            nxt, _ = features.advance_state(output, self._output_normalizer, cur, d, ca, flat[old_name] if old_name else None, cp,
+                                            flat['node_type'], free_types, flat[fallback_name] if fallback_name else None)
+            if not through_state:
+                nxt, cur = nxt.detach(), cur.detach()
+            frame[state_name] = nxt.reshape(W, N, d)
+            if old_name is not None:
+                frame[old_name] = cur.reshape(W, N, d)
+        per_step_losses = torch.stack(losses)
+        return per_step_losses.mean(), per_step_losses.detach()
+
     @torch.no_grad()
     def n_step_computation(self, trajectory: Dict[str, Tensor], n_step: int, num_timesteps=None) -> Tuple[Tensor, Tensor]:
         """Sliding n-step rollouts (flag.py:248-260): every window of n_step + 1 consecutive frames is rolled out from its
@@ -298,6 +361,7 @@ class FlagModel(AbstractSystemModel):
     """src/model/flag.py:17-260."""
     _model_type = 'flag'
     _TYPE_MAP = (0,) + (1,) * 9                  # flag.py:72: class = (node_type != NORMAL)
+    _UNROLL = ('world_pos', 'prev|world_pos', 3, 2.0, -1.0, (NodeType.NORMAL.value,), ('target|world_pos',), None, True)
 
     def __init__(self, params):
         super().__init__(params, node_size=5, edge_size=7)
@@ -445,6 +509,7 @@ class CylinderModel(AbstractSystemModel):
     """src/model/cylinder.py:17-240 (its remote edges use the 'plate' feature rule, cylinder.py:34)."""
     _model_type = 'plate'
     _TYPE_MAP = (0, -1, -1, -1, 1, 2, 3)        # cylinder.py:71-74: INFLOW->1, OUTFLOW->2, WALL_BOUNDARY->3
+    _UNROLL = ('velocity', None, 2, 1.0, 0.0, (NodeType.NORMAL.value, NodeType.OUTFLOW.value), ('target|velocity', 'pressure'), None, True)
 
     def __init__(self, params):
         super().__init__(params, node_size=6, edge_size=3)
@@ -582,6 +647,7 @@ class PlateModel(AbstractSystemModel):
     _model_type = 'plate'
     _TYPE_MAP = (0, 1, 2, 2)                     # plate.py:78: HANDLE (3) -> class 2
     _RADIUS = 0.03                               # plate.py:85
+    _UNROLL = ('world_pos', None, 3, 1.0, 0.0, (NodeType.NORMAL.value,), ('target|world_pos',), 'target|world_pos', False)
 
     def __init__(self, params):
         super().__init__(params, node_size=6, edge_size=8, remote_edge_size=8, edge_sets=('mesh_edges', 'world_edges'))

@@ -17,6 +17,7 @@
  *   model/flag.py:178,188, cylinder.py:163,171  target / integrator arithmetic   -> hgn_lincomb3
  *   model/flag.py:169-180,243, cylinder.py:155-165, plate.py:246-257,328
  *                                    one rollout step's state update            -> hgn_rollout_advance
+ *                                    and its derivative (unrolled training)     -> hgn_rollout_advance_bwd
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
  *                                                                              hgn_normalizer_update, hgn_normalize
  */
@@ -204,6 +205,29 @@ int hgn_rollout_advance(const float* net_out, int64_t ld_out, int out_cols, int 
                         uint32_t free_mask, const float* fallback, int64_t ld_fb, int64_t rows, float* next, int64_t ld_next,
                         float* rec, int64_t ld_rec, int rec_before, float* prev_out, int64_t ld_po, float* inv,
                         int64_t ld_inv, int inv_from, void* stream);
+
+/* ---- backward of the state update (flag.py:169-180,243, cylinder.py:155-165, plate.py:246-257,328) --------------
+ * The exact derivative of what hgn_rollout_advance computes (Normalizer.inverse, then ca*cur + x + cp*prev, then the per-row
+ * choice by node type), for unrolled multi-step training: ONE launch, flat over [rows, F] like the forward, 256 threads per
+ * block, no LDS, no atomics, equal bits on every run.  The statistics are constants (nothing flows into them); s[c] =
+ * max(std[c], eps) is formed from acc_sum / acc_sumsq / acc_count / eps exactly as the forward forms it.
+ * In:  d_next [rows, d] (nullable), d_inv [rows, F - inv_from] (nullable): the gradients of the forward's `next` and `inv`.
+ * Out (each nullable, at least one given): d_net [rows, F], d_cur / d_prev / d_fallback [rows, d].  Every element of every
+ * output given is written exactly once, zeros included: the buffers need no initialisation.
+ * Per element, with g = d_next[r,c] (0 when absent or c >= d) and h = d_inv[r, c - inv_from] (0 when absent or c < inv_from):
+ *   free row (bit node_type[r] of free_mask set; types outside [0, 32) are never free):
+ *     d_net = s[c] * (g + h)     d_cur = ca * g     d_prev = cp * g     d_fallback = 0
+ *   any other row:
+ *     d_net = s[c] * h           d_prev = 0         d_cur = g without a fallback (has_fallback = 0), 0 with one
+ *                                                   d_fallback = g with a fallback, 0 without
+ * No fma contraction: every product and sum is rounded on its own.  Every matrix has its own row stride (>= its row width).
+ * HGN_E_INVALID: null statistics, F outside 1..HGN_MAX_FEATURE_WIDTH, rows outside [0, 2^31), d outside 1..F, inv_from outside
+ * 0..F, a row stride that is zero or smaller than its row, no output asked for, null node_type with rows > 0.  rows = 0: no-op. */
+int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, const float* d_inv, int64_t ld_dinv, int inv_from, int F,
+                            const float* acc_sum, const float* acc_sumsq, const float* acc_count, float eps, int d, float ca,
+                            float cp, const int64_t* node_type, int64_t ldt, uint32_t free_mask, int has_fallback,
+                            int64_t rows, float* d_net, int64_t ld_dnet, float* d_cur, int64_t ld_dcur, float* d_prev,
+                            int64_t ld_dprev, float* d_fallback, int64_t ld_dfb, void* stream);
 
 #ifdef __cplusplus
 }

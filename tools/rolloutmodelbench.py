@@ -4,7 +4,11 @@ eager (`model.replay_rollout = False`).  Per step: build_graph (feature kernels,
     python tools/rolloutmodelbench.py [--steps 100]        prints one JSON object
 With `--nstep-batch M` the object also holds the wall time of ONE n_step_computation (the reference's evaluation after every epoch,
 flag.py:248-260) over `--nstep-frames` frames of the same mesh with windows of `--nstep` steps: the windows one by one (`nstep_batch = None`)
-and in lock step, M windows per union graph (`model.nstep_batch = M`), and whether the two figures agree at rtol 1e-5."""
+and in lock step, M windows per union graph (`model.nstep_batch = M`), and whether the two figures agree at rtol 1e-5.
+With `--unroll N` the tool does one thing instead: it times ONE `unrolled_training_step` of N steps including `backward()`
+(through_state=True, frozen statistics) on the 40x40 flag mesh (none/sum/L15), for `--unroll-windows` windows in lock step and for one
+window, against the same loss written with the ops the package had before that method: per step build_graph_batch -> network ->
+`update` -> torch.where.  The two forms alternate inside one process; the object holds the mean and the smallest time of each."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, 'hyper-graph-nets_amd')):
@@ -42,13 +46,73 @@ def nstep_times(model, frames, a):
     return out
 
 
+def loop_unroll(model, windows, n_steps):
+    """The loss of unrolled_training_step(windows, n_steps, True, False) written with build_graph_batch, `update` and torch.where."""
+    from hgn_amd.system_model import _masked_mse
+    W, N = windows['node_type'].shape[0], windows['node_type'].shape[2]
+    frame = {'cells': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'node_type': windows['node_type'][:, 0],
+             'world_pos': windows['world_pos'][:, 0], 'prev|world_pos': windows['prev|world_pos'][:, 0]}
+    losses = []
+    for t in range(n_steps):
+        frame['target|world_pos'] = windows['target|world_pos'][:, t]
+        graph = model.expand_graph_batch(model.build_graph_batch(frame, False), W, t, n_steps, False)
+        flat = model.flatten_frames(frame)
+        out = model(graph)
+        mask = model._loss_mask(flat)
+        losses.append(_masked_mse(model.get_target(flat, False), out, mask))
+        if t + 1 < n_steps:
+            nxt = torch.where(mask.unsqueeze(1).expand(-1, 3), model.update(flat, out), flat['world_pos'])
+            frame['world_pos'], frame['prev|world_pos'] = nxt.reshape(W, N, 3), flat['world_pos'].reshape(W, N, 3)
+    return torch.stack(losses).mean()
+
+
+def unroll_times(a):
+    from hgn_amd import synthetic, system_model
+    torch.manual_seed(0)
+    model = system_model.FlagModel(params('none', 0, 15, 'sum'))
+    warm = {k: v.cuda() for k, v in synthetic.flag_frame(seed=100, nx=40, ny=40).items()}
+    with torch.no_grad():
+        model.learned_model(model.build_graph(warm, True))
+        model.get_target(warm, True)
+    res = {'n_steps': a.unroll, 'nodes': 1600, 'message_passing_steps': 15, 'repeats': a.unroll_repeats}
+    for W in dict.fromkeys((a.unroll_windows, 1)):
+        frames = [[synthetic.flag_frame(seed=200 + 10 * w + t, nx=40, ny=40) for t in range(a.unroll)] for w in range(W)]
+        windows = {k: torch.stack([torch.stack([f[k] for f in row]) for row in frames]).cuda()
+                   for k in ('world_pos', 'prev|world_pos', 'target|world_pos', 'node_type')}
+        windows['cells'], windows['mesh_pos'] = warm['cells'], warm['mesh_pos']
+        forms = {'unrolled_training_step': lambda: model.unrolled_training_step(windows, a.unroll, True, False)[0],
+                 'per_step_ops': lambda: loop_unroll(model, windows, a.unroll)}
+        times, losses = {k: [] for k in forms}, {}
+        for rep in range(2 + a.unroll_repeats):                # two warm rounds: lazy state, topology caches
+            for name, fn in forms.items():
+                model.zero_grad(set_to_none=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                loss = fn()
+                loss.backward()
+                torch.cuda.synchronize()
+                if rep >= 2:
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+                losses[name] = float(loss.detach())
+        res[f'W={W}'] = {f'{k}_ms': {'mean': sum(v) / len(v), 'min': min(v)} for k, v in times.items()}
+        res[f'W={W}']['losses_equal'] = losses['unrolled_training_step'] == losses['per_step_ops']
+        res[f'W={W}']['speedup_of_the_means'] = (res[f'W={W}']['per_step_ops_ms']['mean'] / res[f'W={W}']['unrolled_training_step_ms']['mean'])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--unroll', type=int, default=0, help='time one unrolled_training_step of N steps with backward() instead')
+    ap.add_argument('--unroll-windows', type=int, default=8)
+    ap.add_argument('--unroll-repeats', type=int, default=10)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--nstep-batch', type=int, default=0, help='also time one n_step_computation with model.nstep_batch = M and without')
     ap.add_argument('--nstep', type=int, default=60)
     ap.add_argument('--nstep-frames', type=int, default=120)
     a = ap.parse_args()
+    if a.unroll > 0:
+        print(json.dumps(unroll_times(a)))
+        return
     from hgn_amd import synthetic, system_model
     res = {}
     for name, connector, K, layers, agg in (('flag none/sum/L15', 'none', 0, 15, 'sum'), ('flag hyper/pna/L5/K16', 'hyper', 16, 5, 'pna')):
