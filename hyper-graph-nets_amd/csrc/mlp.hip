@@ -376,6 +376,10 @@ extern "C" int hgn_mlp_bwd(const hgn_mlp_bwd_t* a, void* stream) {
         return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: max/min need the saved arg index");
     }
   }
+  // a 128-wide d_out is read with 16-byte loads by every kernel of this entry (load_dout; with a residual dx, t_add): refused
+  // otherwise, as the forward refuses such a residual.  A narrower d_out (decoder) takes the masked scalar loads at any address.
+  if (a->d_out && a->out_w == 128 && ((a->ld_dout & 3) || !aligned16(a->d_out)))
+    return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: a 128-wide d_out must be 16-byte aligned, ld_dout a multiple of 4");
   if (a->ln_ws && (!a->ln_g || !a->d_gamma || !a->d_beta)) return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: LayerNorm gradient outputs missing");
   for (int i = 0; i < a->n_dx; ++i)
     if (!a->dx[i].W || !a->dx[i].dx || a->dx[i].K < 1 || (a->dx[i].residual && (a->dx[i].K != 128 || a->out_w != 128)))

@@ -195,6 +195,8 @@ __device__ __forceinline__ void add_agg_dout(Act& g, const hgn_mlp_bwd_t& a, lon
 }
 
 // d_out_eff of the lane's row: d_out (optional) + the aggregation backward scattered back through the CSR row of the edge.
+// A 128-wide d_out reaches a kernel 16-byte aligned with ld_dout % 4 == 0 only (hgn_mlp_bwd refuses anything else before it
+// launches): the 16-byte t_load / t_add below never see another address.  A narrower one is read element by element.
 template <bool ACC>
 __device__ __forceinline__ void load_dout(Act& g, const hgn_mlp_bwd_t& a, long rc, int kq, int pre_seg = -1) {
   // ACC: add d_out_eff to g (residual path; 128-wide, aligned);  otherwise g = d_out_eff

@@ -194,13 +194,32 @@ def _workspace(device, nbytes: int, tag: str = 'wgrad') -> torch.Tensor:
 
 
 def _rowmajor(t: torch.Tensor) -> torch.Tensor:
-    """2-D tensor whose rows are contiguous (row stride arbitrary) and 16-byte aligned; copies otherwise."""
+    """The form in which a 2-D operand's address goes into an argument struct: fp32, unit column stride, rows that do not overlap
+    (row stride >= width) and -- for a width that is a multiple of 4 -- a 16-byte aligned base with a row stride (`_ld`) that is a
+    multiple of 4 floats, i.e. every row 16-byte aligned.  Copies otherwise.
+
+    The rule: AN OPERAND'S LAYOUT NEVER CHANGES WHICH KERNELS RUN, NOR A BIT OF THE RESULT.  The kernels pick 16-byte or scalar
+    loads per operand from its address, its leading dimension and its width; a layout the vector paths cannot take is copied here,
+    so that they always run (and no entry point refuses the call).
+      in place:  contiguous tensors, row slices (big[:M]), wider rows on an aligned base (buf[:, :K] of a [M, K + 4] buffer),
+                 every second row (big[::2]);
+      copied:    a column offset that is no multiple of 4 floats (buf[:, 1:1 + K]), a row stride that is no multiple of 4 floats
+                 (buf[:, :K] of a [M, K + 1] buffer; what torch.cat's backward hands the producers of its inputs), transposes,
+                 expanded (stride 0) tensors, other dtypes.
+    A narrow operand whose width is not a multiple of 4 (encoder inputs, a 3-wide decoder gradient) has no aligned rows in any
+    layout: it stays in place and the kernels read it on their masked scalar path.
+    (One operand asks for more: the upstream gradient of an edge block's e' also serves as `base` of the streaming aggregation
+    backward, which takes dense rows -- EdgeBlockFn.backward copies any other row stride, for every aggregation alike.)"""
     if t.dim() != 2:
         raise ValueError('expected a 2-D tensor')
     if t.dtype != torch.float32:
         t = t.float()
-    if t.shape[1] > 0 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
+    M, W = t.shape
+    if (W > 0 and t.stride(1) != 1) or (M > 1 and t.stride(0) < W):
+        return t.contiguous()
+    if W > 0 and W % 4 == 0 and (t.data_ptr() % 16 != 0 or _ld(t) % 4 != 0):
+        # (not .contiguous(): a one-row or offset view of a flat buffer IS contiguous and would come back as it is)
+        t = t.clone(memory_format=torch.contiguous_format)
     return t
 
 
@@ -730,6 +749,11 @@ class _JoinFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h):
         ctx.set_materialize_grads(False)
+        # The table is keyed by address: the rows are put into the form the kernels take (_rowmajor) HERE, once, so that both
+        # consumers get the same tensor and neither makes a copy of its own -- a misaligned view of a latent would otherwise be
+        # copied by each, the two copies would never meet in the table, and the layout would decide how d(h) is summed.
+        if h.dim() == 2:
+            h = _rowmajor(h)
         ctx.hgn, ctx.key = current(), h.data_ptr()
         return h.detach(), h.detach()
 
@@ -978,7 +1002,7 @@ class EdgeBlockFn(torch.autograd.Function):
         else:
             P = (torch.empty(Ns, LAT, device=dev), torch.empty(Nr, LAT, device=dev))
             Ps, Pr, ldp = P[0].data_ptr(), P[1].data_ptr(), LAT
-        pk = packs_of(w, ctx=c) if (all(_ld(h) % 4 == 0 and h.data_ptr() % 16 == 0 for h in (h_s, h_r)) and not c.fp32_only()) else None
+        pk = packs_of(w, ctx=c) if not c.fp32_only() else None      # (whatever layout h came in: _rowmajor has aligned its rows)
         # the `sum` aggregate formed inside the edge kernel needs a zero-filled [N, 128] buffer: filled by the pre-projection launch,
         # which passes over the same node rows anyway (hgn_linear_fwd6z), instead of a launch of its own
         agg_zeroed = None
@@ -1094,7 +1118,9 @@ class EdgeBlockFn(torch.autograd.Function):
         b.out_w = LAT
         if d_out is not None:
             d_out = _rowmajor(d_out)
-            b.d_out = d_out.data_ptr(); b.ld_dout = _ld(d_out)
+            if _ld(d_out) != LAT:          # the streaming pre-passes below take d_out as `base`: dense rows.  One form for every layout
+                d_out = d_out.clone(memory_format=torch.contiguous_format)
+            b.d_out = d_out.data_ptr(); b.ld_dout = LAT
         g_eff = None
         if d_agg is not None and std_saved is not None:
             # 'std' needs e', the aggregate and the mean, for which hgn_mlp_bwd_t has no room: the gradient that reaches e' -- d(e') + the
@@ -1143,7 +1169,7 @@ class EdgeBlockFn(torch.autograd.Function):
         # One pass for data gradients AND weight gradients (include/hgn_mp.h: hgn_edge_bwd_fused): dz3 / dz2 never reach memory.
         may_fuse = c.fused() and pk_t is not None and E > 0 and c.wgrad_stream is None and accs[2] == accs[4]
         fused = may_fuse and bool(L.hgn_edge_bwd_fused_eligible(C.byref(b)))      # (dW3 / dW2 share one accumulate flag in hgn_wfuse_t)
-        if may_fuse and not fused and d_agg is not None and (d_out is None or _ld(d_out) == LAT):
+        if may_fuse and not fused and d_agg is not None:
             # Several aggregates (pna) or arg-routed ones: the fused kernel gathers ONE `sum` row per edge.  The gradient that reaches e'
             # -- d(e') + the aggregation backward scattered back to the edge rows -- is formed once by the streaming kernel
             # (hgn_segment_reduce_bwd with `base`: the same values added in the same order as hgn_mlp_bwd's in-register d_out_eff)
@@ -1253,11 +1279,12 @@ class EdgeBlockFn(torch.autograd.Function):
 
 
 def _std_prepass(L, st, topo, agg_ops, amax, amin, std_saved, d_agg, d_out, E, Nr, off_r, dev):
-    """-> g_eff [E, 128] = d(e') + the backward of an aggregation whose list contains 'std' (hgn_segment_reduce5_bwd[_sorted])."""
+    """-> g_eff [E, 128] = d(e') + the backward of an aggregation whose list contains 'std' (hgn_segment_reduce5_bwd[_sorted]).
+    `d_agg` comes through _rowmajor, `d_out` (nullable) as dense 16-byte aligned [E, 128] rows: EdgeBlockFn.backward sees to both."""
     e2, agg, smean = std_saved
     arr, codes = _ops_array(agg_ops)
-    if d_out is not None and (_ld(d_out) != LAT or d_out.data_ptr() % 16):
-        d_out = d_out.contiguous()
+    if d_out is not None and (_ld(d_out) != LAT or d_out.data_ptr() % 16 != 0):
+        raise _lib.HgnError('_std_prepass: d_out must be dense, 16-byte aligned [E, 128] rows')
     g_eff = torch.empty(E, LAT, device=dev)
     ap = amax.data_ptr() if amax is not None else 0
     an = amin.data_ptr() if amin is not None else 0

@@ -280,6 +280,10 @@ typedef struct {
 
 typedef struct {
   int64_t M;
+  /* d_out [M, out_w], leading dimension ld_dout.  out_w == 128: d_out must be 16-byte aligned and ld_dout a multiple of 4 -- every
+   * kernel reads it (and, for a `residual` dx, adds it) with 16-byte loads; any other address or stride is REFUSED with
+   * HGN_E_INVALID before a launch, as hgn_mlp_fwd refuses such a `res`.  The caller copies (hgn_amd/ops.py: _rowmajor).
+   * out_w < 128 (decoder): any address and stride, read element by element. */
   const float* d_out; int64_t ld_dout; int32_t out_w;
   const float* ln_g; const float* xhat; const float* rstd;    /* nullable triple        */
   const float* z2; const float* z1;
