@@ -22,12 +22,27 @@ def _f32_rows(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def _ld(t: torch.Tensor) -> int:
+def _ld(t) -> int:
+    """Row stride of a 2-D tensor in elements; 0 for an absent (None) one."""
+    if t is None:
+        return 0
     return t.stride(0) if t.shape[0] > 1 else max(int(t.shape[1]), 1)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 def _ids(t: torch.Tensor, dev) -> torch.Tensor:
     return t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def _type_column(node_type: torch.Tensor, dev, rows: int):
+    """The reference's ``node_type`` ([rows, 1] or [rows]) as int64 on ``dev`` -> (column 0, its stride in elements)."""
+    nt = node_type.to(device=dev, dtype=torch.int64)
+    if nt.dim() == 2:
+        nt = nt[:, 0]
+    return nt, (nt.stride(0) if rows > 1 else 1)
 
 
 def cells_to_edges(cells: torch.Tensor, deform: bool = False):
@@ -96,12 +111,11 @@ def rel_edge_features_bwd(d_feat, d_len, a: torch.Tensor, b, senders: torch.Tens
     cs = cr = None
     if E > 0:
         cs, cr = topology.segment_csr(s, N, dev), topology.segment_csr(r, N, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     _lib.check(_lib.lib().hgn_rel_edge_features_bwd(
-        ptr(d_feat), _ld(d_feat) if d_feat is not None else 0, ptr(d_len), a.data_ptr(), _ld(a), da,
+        _ptr(d_feat), _ld(d_feat), _ptr(d_len), a.data_ptr(), _ld(a), da,
         b.data_ptr() if db else None, _ld(b) if db else 0, db, N, s.data_ptr(), r.data_ptr(), E,
-        ptr(cs.rowptr) if cs else None, ptr(cs.perm) if cs else None, ptr(cr.rowptr) if cr else None,
-        ptr(cr.perm) if cr else None, cs.max_rows + cr.max_rows if cs else 0, ptr(d_a), ptr(d_b), _lib.stream_ptr()),
+        _ptr(cs.rowptr) if cs else None, _ptr(cs.perm) if cs else None, _ptr(cr.rowptr) if cr else None,
+        _ptr(cr.perm) if cr else None, cs.max_rows + cr.max_rows if cs else 0, _ptr(d_a), _ptr(d_b), _lib.stream_ptr()),
         'hgn_rel_edge_features_bwd')
     return d_a, d_b
 
@@ -186,10 +200,7 @@ class _NodeFeaturesFn(torch.autograd.Function):
         d_out = _f32_rows(d_out)
         N = d_out.shape[0]
         d = d_out.shape[1] - n_classes
-        nt = node_type.to(device=dev, dtype=torch.int64)
-        if nt.dim() == 2:
-            nt = nt[:, 0]
-        ldt = nt.stride(0) if N > 1 else 1
+        nt, ldt = _type_column(node_type, dev, N)
         d_cur = torch.empty(N, d, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         d_prev = torch.empty(N, d, dtype=torch.float32, device=dev) if prev is not None and ctx.needs_input_grad[1] else None
         _lib.check(_lib.lib().hgn_node_features_bwd(
@@ -208,11 +219,8 @@ def node_features(cur, prev, node_type: torch.Tensor, mapping, n_classes: int, v
     if _needs_grad(cur, prev):
         return _NodeFeaturesFn.apply(cur, prev, node_type, mapping, n_classes, vel_first, vel_mask_type, d)
     dev = node_type.device
-    nt = node_type.to(torch.int64)
-    if nt.dim() == 2:
-        nt = nt[:, 0]
-    N = nt.shape[0]
-    ldt = nt.stride(0) if N > 1 else 1
+    N = node_type.shape[0]
+    nt, ldt = _type_column(node_type, dev, N)
     if cur is not None:
         cur = _f32_rows(cur.to(dev))
         d = cur.shape[1]
@@ -376,12 +384,9 @@ def rollout_advance(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int
         fallback = _f32_rows(fallback.to(dev))
         if fallback.shape != cur.shape:
             raise ValueError('rollout_advance: cur / fallback shape mismatch')
-    nt = node_type.to(device=dev, dtype=torch.int64)
-    if nt.dim() == 2:
-        nt = nt[:, 0]
+    nt, ldt = _type_column(node_type, dev, rows)
     if nt.shape[0] != rows:
         raise ValueError(f'rollout_advance: {nt.shape[0]} node types for {rows} rows')
-    ldt = nt.stride(0) if rows > 1 else 1
     free_mask = 0
     for t in free_types:
         if not 0 <= int(t) < 32:
@@ -394,13 +399,11 @@ def rollout_advance(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int
         _out_rows(prev_out, rows, d, 'prev_out')
     if inv_out is not None:
         _out_rows(inv_out, rows, F - int(inv_from), 'inv_out')
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    ld = lambda t: _ld(t) if t is not None else 0
     _lib.check(_lib.lib().hgn_rollout_advance(
         x.data_ptr(), _ld(x), cols, F, normalizer._acc_sum.data_ptr(), normalizer._acc_sum_squared.data_ptr(),
-        normalizer._acc_count.data_ptr(), float(normalizer._eps), cur.data_ptr(), _ld(cur), d, float(ca), ptr(prev), ld(prev),
-        float(cp), nt.data_ptr(), ldt, free_mask, ptr(fallback), ld(fallback), rows, next_out.data_ptr(), _ld(next_out),
-        ptr(rec), ld(rec), 1 if rec_before else 0, ptr(prev_out), ld(prev_out), ptr(inv_out), ld(inv_out), int(inv_from),
+        normalizer._acc_count.data_ptr(), float(normalizer._eps), cur.data_ptr(), _ld(cur), d, float(ca), _ptr(prev), _ld(prev),
+        float(cp), nt.data_ptr(), ldt, free_mask, _ptr(fallback), _ld(fallback), rows, next_out.data_ptr(), _ld(next_out),
+        _ptr(rec), _ld(rec), 1 if rec_before else 0, _ptr(prev_out), _ld(prev_out), _ptr(inv_out), _ld(inv_out), int(inv_from),
         _lib.stream_ptr()), 'hgn_rollout_advance')
     return next_out
 
@@ -424,9 +427,8 @@ class _AdvanceStateFn(torch.autograd.Function):
         det = lambda t: t.detach() if t is not None else None
         nxt, inv = _advance_into_fresh(net_out.detach(), normalizer, cur.detach(), d, ca, det(prev), cp, node_type, free_types,
                                        det(fallback), inv_from)
-        nt = node_type.to(device=net_out.device, dtype=torch.int64)
-        ctx.cfg = (float(normalizer._eps), d, ca, cp, nt[:, 0] if nt.dim() == 2 else nt, sum(1 << int(t) for t in set(free_types)),
-                   int(inv_from or 0), net_out, cur, prev, fallback)
+        ctx.cfg = (float(normalizer._eps), d, ca, cp, _type_column(node_type, net_out.device, nxt.shape[0]),
+                   sum(1 << int(t) for t in set(free_types)), int(inv_from or 0), net_out, cur, prev, fallback)
         ctx.save_for_backward(normalizer._acc_sum.detach().clone(), normalizer._acc_sum_squared.detach().clone(),
                               normalizer._acc_count.detach().clone())
         return nxt, inv
@@ -434,7 +436,7 @@ class _AdvanceStateFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_next, d_inv):
-        eps, d, ca, cp, nt, free_mask, inv_from, net_out, cur, prev, fallback = ctx.cfg
+        eps, d, ca, cp, (nt, ldt), free_mask, inv_from, net_out, cur, prev, fallback = ctx.cfg
         acc_sum, acc_sumsq, acc_count = ctx.saved_tensors
         dev, F, rows = acc_sum.device, acc_sum.numel(), nt.shape[0]
         g = _f32_rows(d_next.to(dev)) if d_next is not None else None         # an incoming gradient may have any stride
@@ -443,12 +445,10 @@ class _AdvanceStateFn(torch.autograd.Function):
                 fallback is not None and ctx.needs_input_grad[3]]
         outs = [torch.empty(rows, w, dtype=torch.float32, device=dev) if need else None for need, w in zip(want, (F, d, d, d))]
         if any(want):
-            ptr = lambda t: t.data_ptr() if t is not None else None
-            ld = lambda t: _ld(t) if t is not None else 0
             _lib.check(_lib.lib().hgn_rollout_advance_bwd(
-                ptr(g), ld(g), ptr(h), ld(h), inv_from, F, acc_sum.data_ptr(), acc_sumsq.data_ptr(), acc_count.data_ptr(), eps, d,
-                ca, cp, nt.data_ptr(), nt.stride(0) if rows > 1 else 1, free_mask, 1 if fallback is not None else 0, rows,
-                ptr(outs[0]), ld(outs[0]), ptr(outs[1]), ld(outs[1]), ptr(outs[2]), ld(outs[2]), ptr(outs[3]), ld(outs[3]),
+                _ptr(g), _ld(g), _ptr(h), _ld(h), inv_from, F, acc_sum.data_ptr(), acc_sumsq.data_ptr(), acc_count.data_ptr(), eps, d,
+                ca, cp, nt.data_ptr(), ldt, free_mask, 1 if fallback is not None else 0, rows,
+                _ptr(outs[0]), _ld(outs[0]), _ptr(outs[1]), _ld(outs[1]), _ptr(outs[2]), _ld(outs[2]), _ptr(outs[3]), _ld(outs[3]),
                 _lib.stream_ptr()), 'hgn_rollout_advance_bwd')
         refs = (net_out, cur, prev, fallback)
         return tuple(_like(o, r) if o is not None else None for o, r in zip(outs, refs)) + (None,) * 7
@@ -474,11 +474,8 @@ def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, send
     _lib.require_gpu(pos)
     dev = pos.device
     pos = _f32_rows(pos)
-    nt = node_type.to(device=dev, dtype=torch.int64)
-    if nt.dim() == 2:
-        nt = nt[:, 0]
     N = pos.shape[0]
-    ldt = nt.stride(0) if N > 1 else 1
+    nt, ldt = _type_column(node_type, dev, N)
     L = _lib.lib()
     nb = C.c_size_t(0)
     _lib.check(L.hgn_radius_edges_workspace_bytes(N, C.byref(nb)), 'hgn_radius_edges_workspace_bytes')
@@ -486,8 +483,7 @@ def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, send
     offsets = torch.empty(N + 1, dtype=torch.int32, device=dev)
     total = C.c_int64(0)
     args = (pos.data_ptr(), _ld(pos), pos.shape[1], nt.data_ptr(), ldt, N, float(radius), int(sender_type),
-            int(receiver_type), nbr_rowptr.data_ptr() if nbr_rowptr is not None else None,
-            nbr.data_ptr() if nbr is not None else None)
+            int(receiver_type), _ptr(nbr_rowptr), _ptr(nbr))
     _lib.check(L.hgn_radius_edges_count(*args, offsets.data_ptr(), C.byref(total), ws.data_ptr(), ws.numel(),
                                         _lib.stream_ptr()), 'hgn_radius_edges_count')
     s = torch.empty(total.value, dtype=torch.int64, device=dev)
@@ -509,14 +505,11 @@ def radius_edges_batch(pos: torch.Tensor, node_type: torch.Tensor, n_graphs: int
     _lib.require_gpu(pos)
     dev = pos.device
     pos = _f32_rows(pos)
-    nt = node_type.to(device=dev, dtype=torch.int64)
-    if nt.dim() == 2:
-        nt = nt[:, 0]
     rows, B = pos.shape[0], int(n_graphs)
+    nt, ldt = _type_column(node_type, dev, rows)
     if B < 1 or rows % B or nt.shape[0] != rows:
         raise ValueError(f'radius_edges_batch: {rows} position rows / {nt.shape[0]} node types do not split into {B} graphs of equal size')
     N = rows // B
-    ldt = nt.stride(0) if rows > 1 else 1
     L = _lib.lib()
     nb = C.c_size_t(0)
     _lib.check(L.hgn_radius_edges_batch_workspace_bytes(B, N, C.byref(nb)), 'hgn_radius_edges_batch_workspace_bytes')
@@ -525,8 +518,7 @@ def radius_edges_batch(pos: torch.Tensor, node_type: torch.Tensor, n_graphs: int
     graph_offsets = torch.empty(B + 1, dtype=torch.int32, device=dev)
     total = C.c_int64(0)
     args = (pos.data_ptr(), _ld(pos), pos.shape[1], nt.data_ptr(), ldt, B, N, float(radius), int(sender_type),
-            int(receiver_type), nbr_rowptr.data_ptr() if nbr_rowptr is not None else None,
-            nbr.data_ptr() if nbr is not None else None)
+            int(receiver_type), _ptr(nbr_rowptr), _ptr(nbr))
     _lib.check(L.hgn_radius_edges_batch_count(*args, offsets.data_ptr(), graph_offsets.data_ptr(), C.byref(total),
                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'hgn_radius_edges_batch_count')
     s = torch.empty(total.value, dtype=torch.int64, device=dev)

@@ -9,7 +9,8 @@ computed once per ``cells`` tensor and reused for the whole trajectory (the refe
 flag.py:76-78).
 """
 import math
-from typing import Dict, Tuple
+from functools import reduce
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn, Tensor
@@ -36,6 +37,26 @@ def _masked_mse(target: Tensor, output: Tensor, mask: Tensor) -> Tensor:
     return (((output - target) ** 2) * m).sum() / (m.sum() * output.shape[1])
 
 
+class LockStep(NamedTuple):
+    """What one model integrates, one instance per model class: read by `_loss_mask`, `validation_step`, `rollout_batch` and
+    `unrolled_training_step`.  `d`, `ca`, `cp`, `free_types` and the fallback are the arguments of features.rollout_advance /
+    advance_state: next = ca * state + output[:, :d] + cp * previous on the rows whose node type is free, the fallback elsewhere."""
+    state: str                      # the series that is integrated
+    prev: Optional[str]             # the series that receives the old state, or None
+    d: int
+    ca: float
+    cp: float
+    free_types: Tuple[int, ...]     # node types that are integrated (and enter the loss)
+    per_step: Tuple[str, ...]       # the per-step series get_target reads
+    fallback: Optional[str]         # the per-step series a row that is not free is put on; None: it keeps its own state
+    differentiable: bool            # whether build_graph_batch is differentiable with respect to the state
+    expand_steps: Optional[int]     # the num_steps a rollout hands to expand_graph_batch; None: the call's own
+    record_before: bool             # a rollout records the state before the step (else the new one)
+    inv_from: Optional[int]         # `inv_out` holds the inverse-normalised output columns from here on; None: not recorded
+    errors: str                     # the series the recorded states are compared against
+    target: str                     # the series validation_step compares the updated state against
+
+
 class AbstractSystemModel(nn.Module):
     """The reference's system-model base (abstract_system_model.py:10-190) together with the constructor logic its three
     subclasses repeat (flag.py:21-63, cylinder.py:21-63, plate.py:21-67): normalisers, the optional graph balancer and remote
@@ -43,6 +64,12 @@ class AbstractSystemModel(nn.Module):
     reference's trainer / pickles touch (`learned_model`, `_*_normalizer`, `_rmp`, `_balancer`, `_remote_graph`,
     `_graph_balancer`, `message_passing_steps`, ...) are kept."""
     _model_type = None
+    _LOCKSTEP: LockStep = None
+    # Run-time state, not model state: the captured HIP graphs of the rollout replay, the edges of the last mesh (`_mesh_edges`), of
+    # the last union (`_union_mesh_edges`) and the plate's neighbour list (`_mesh_neighbours`).  Class-level defaults, so a model
+    # unpickled from a checkpoint that lacks some of them starts with empty caches.
+    _RUNTIME_CACHES = ('_fwd_cache', '_cells_key', '_cells_edges', '_batch_edges_key', '_batch_edges', '_nbr_key', '_nbr')
+    _fwd_cache = _cells_key = _cells_edges = _batch_edges_key = _batch_edges = _nbr_key = _nbr = None
 
     def __init__(self, params, node_size: int, edge_size: int, remote_edge_size: int = 7,
                  edge_sets=('mesh_edges',)) -> None:
@@ -70,7 +97,6 @@ class AbstractSystemModel(nn.Module):
         self.message_passing_aggregator = params.get('aggregation')
         self._visualized = False
         self.replay_rollout = True          # forward() without gradients replays a captured HIP graph per topology (graphs.GraphedForwardCache)
-        self._fwd_cache = None
         self._edge_sets = list(edge_sets)
         if self._balancer:
             from . import graph_balancer as _gb
@@ -85,20 +111,13 @@ class AbstractSystemModel(nn.Module):
             message_passing_steps=self.message_passing_steps,
             message_passing_aggregator=self.message_passing_aggregator,
             architecture=self._architecture, edge_sets=self._edge_sets).to(device)
-        self._cells_key = None
-        self._cells_edges = None
 
     def __getstate__(self):
         """The reference pickles the whole system model at every checkpoint (MeshSimulator.py:492-493 `pickle.dump(self)`, with
         `_network` inside) and deep-copies it for evaluation.  Captured HIP graphs (the rollout replay cache) and the per-mesh
         edge caches are run-time state, not model state: a copy starts without them and captures again on its own device."""
         state = super().__getstate__()
-        state['_fwd_cache'] = None
-        state['_cells_key'] = None
-        state['_cells_edges'] = None
-        for name in ('_batch_edges_key', '_batch_edges'):                # the union's mesh edges: rebuilt from the mesh on first use
-            if name in state:
-                state[name] = None
+        state.update(dict.fromkeys(self._RUNTIME_CACHES))
         return state
 
     def _select_architecture(self, connector):
@@ -118,7 +137,7 @@ class AbstractSystemModel(nn.Module):
     def _union_mesh_edges(self, senders: Tensor, receivers: Tensor, n_graphs: int, num_nodes: int):
         """Mesh edges of the disjoint union of ``n_graphs`` copies of one mesh: the ids of copy b are shifted by b * num_nodes
         (what batching.batch_graphs does), graph-major.  Built once per (mesh, batch size, node count)."""
-        key = getattr(self, '_batch_edges_key', None)                    # (B, N, the mesh's sender tensor: _mesh_edges caches it)
+        key = self._batch_edges_key                                      # (B, N, the mesh's sender tensor: _mesh_edges caches it)
         if key is None or key[0] != n_graphs or key[1] != num_nodes or key[2] is not senders:
             off = (torch.arange(n_graphs, device=senders.device) * num_nodes).repeat_interleave(senders.shape[0])
             self._batch_edges = ((senders.repeat(n_graphs) + off).contiguous(), (receivers.repeat(n_graphs) + off).contiguous())
@@ -133,6 +152,24 @@ class AbstractSystemModel(nn.Module):
         if t.dim() == 2:
             t = t.unsqueeze(0).expand(n_graphs, num_nodes, -1)
         return t.reshape(n_graphs * num_nodes, -1).contiguous()
+
+    def _frame_rows(self, inputs: Dict, names, batched: bool):
+        """What the one body behind build_graph and build_graph_batch works on: -> (rows, B, N), the series ``names`` and
+        `mesh_pos` on the device.  A single frame: as they are, B is None.  A batch: [B, N, .] flattened to the [B*N, .] rows of the
+        union (views: no launch), a shared `mesh_pos` repeated (`_union_rows`: the one copy a batch adds)."""
+        rows = {name: inputs[name].to(device) for name in names}
+        if not batched:
+            rows['mesh_pos'] = inputs['mesh_pos'].to(device)
+            return rows, None, rows['node_type'].shape[0]
+        B, N = rows[names[0]].shape[0], rows[names[0]].shape[1]
+        rows = {name: t.reshape(B * N, -1) for name, t in rows.items()}
+        rows['mesh_pos'] = self._union_rows(inputs, 'mesh_pos', B, N)
+        return rows, B, N
+
+    def _frame_edges(self, cells: Tensor, B, N: int, deform: bool = False):
+        """-> ((senders, receivers) of the frame, or of the union of B frames when B is not None; those of the one mesh)."""
+        mesh = self._mesh_edges(cells, deform)
+        return (mesh if B is None else self._union_mesh_edges(*mesh, B, N)), mesh
 
     @staticmethod
     def flatten_frames(inputs: Dict) -> Dict:
@@ -214,6 +251,30 @@ class AbstractSystemModel(nn.Module):
         for module in (self, self.learned_model):
             module.eval()
 
+    # ---- one training and one validation step for the three models ------------------------------------------------
+    def _loss_mask(self, data_frame):
+        """The rows whose node type is free (they are integrated, and only they enter the loss): one `eq` per free type."""
+        t = data_frame['node_type'].to(device)[:, 0]
+        return reduce(torch.logical_or, [torch.eq(t, value) for value in self._LOCKSTEP.free_types])
+
+    def training_step(self, graph, data_frame):
+        """flag.py:146-154, cylinder.py:123-136, plate.py:218-228."""
+        network_output = self(graph)
+        target_normalized = self.get_target(data_frame)
+        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
+
+    @torch.no_grad()
+    def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
+        """flag.py:156-167, cylinder.py:138-153, plate.py:230-244: -> (loss, error of the updated state against the target series)."""
+        prediction = self(graph)
+        target_normalized = self.get_target(data_frame, False)
+        mask = self._loss_mask(data_frame)
+        loss = _masked_mse(target_normalized, prediction, mask).item()
+        updated = self.update(data_frame, prediction)
+        new_state = updated if torch.is_tensor(updated) else updated[0]      # the flag's update returns the state alone
+        state_error = _masked_mse(data_frame[self._LOCKSTEP.target].to(device), new_state, mask).item()
+        return loss, state_error
+
     # ---- evaluation helpers shared by the three models ------------------------------------------------------------
     @staticmethod
     def _first_frame(trajectory: Dict[str, Tensor]) -> Dict[str, Tensor]:
@@ -249,6 +310,54 @@ class AbstractSystemModel(nn.Module):
         truth = windows[name][:, :slab.shape[0]].to(device).transpose(0, 1)
         return self._per_step_mse(truth, slab).transpose(0, 1)
 
+    @torch.no_grad()
+    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int):
+        """Not in the reference: `rollout` for W windows of ONE mesh at once.  The state series, the series that holds the old state
+        (flag), the per-step fallback (plate: the scripted `target|world_pos`) and `node_type` are [W, T, N, .] (window w may be a
+        view of a longer trajectory); `cells` and a `mesh_pos` shared by all windows are given once.  The W windows advance in lock
+        step: every step is one build_graph_batch over the W current states (is_training=False; for the plate one radius query for
+        all windows), expand_graph_batch, the network, and ONE features.rollout_advance launch with the constants of `_LOCKSTEP`.
+        It integrates the free rows, keeps or scripts the others and writes the new state, the recorded row and the model's extra
+        records (`_rollout_records`) straight into their slices of [steps, W, N, .] slabs.  -> `_rollout_result`: per window what
+        `rollout` returns for it, stacked as [W, steps, N, .], and the errors [W, steps]."""
+        ls = self._LOCKSTEP
+        if num_steps is None:
+            num_steps = windows[ls.state].shape[1]
+        cells, mesh_pos = self._shared_mesh(windows)
+        cur = self._window_start(windows, ls.state)
+        prev = self._window_start(windows, ls.prev) if ls.prev else None
+        node_type = self._window_start(windows, 'node_type').to(torch.int64)
+        W, N = cur.shape[0], cur.shape[1]
+        rows = lambda t: t.view(W * N, -1)
+        scripted = None
+        if ls.fallback:                                                 # [steps, W, N, d], transposed once
+            scripted = windows[ls.fallback][:, :num_steps].to(device).transpose(0, 1).contiguous()
+        slab = torch.empty(num_steps, W, N, ls.d, dtype=torch.float32, device=cur.device)
+        records = self._rollout_records(lambda width: torch.empty(num_steps, W, N, width, dtype=torch.float32, device=cur.device))
+        nxt, prev_nxt = torch.empty_like(cur), (torch.empty_like(prev) if ls.prev else None)
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
+        for step in range(num_steps):
+            frame[ls.state] = cur
+            if ls.prev:
+                frame[ls.prev] = prev
+            if ls.fallback:
+                frame[ls.fallback] = scripted[step]
+            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, ls.expand_steps or num_steps,
+                                            is_training=False)
+            outputs = {name: rows(record[step]) for name, record in records.items()}
+            if ls.prev:
+                outputs['prev_out'] = rows(prev_nxt)                    # the old state goes into the swap buffer
+            features.rollout_advance(self(graph), self._output_normalizer, rows(cur), ls.d, ls.ca, rows(prev) if ls.prev else None,
+                                     ls.cp, rows(node_type), ls.free_types, rows(scripted[step]) if ls.fallback else None, rows(nxt),
+                                     rec=rows(slab[step]), rec_before=ls.record_before, inv_from=ls.inv_from or 0, **outputs)
+            cur, nxt, prev, prev_nxt = nxt, cur, prev_nxt, prev
+        return (self._rollout_result(windows, node_type, slab.transpose(0, 1), **{k: v.transpose(0, 1) for k, v in records.items()}),
+                self._batch_errors(windows, ls.errors, slab))
+
+    def _rollout_records(self, empty) -> Dict[str, Tensor]:
+        """The slabs a model records beside the state, by the rollout_advance output that fills them; ``empty(width)`` makes one."""
+        return {}
+
     @staticmethod
     def window_views(trajectory: Dict[str, Tensor], n_step: int, frames: int) -> Dict[str, Tensor]:
         """All frames - n_step sliding windows of n_step + 1 frames as strided views of the trajectory's series ([T, ...] ->
@@ -263,11 +372,6 @@ class AbstractSystemModel(nn.Module):
         return views
 
     # ---- training on unrolled rollouts: the W windows advance in lock step, with autograd ---------------------------------
-    # Per model: (state series, the series that receives the old state or None, d, ca, cp, free node types, the per-step series
-    # get_target reads, the per-step series a row that is not free falls back to or None: its own state,
-    # whether build_graph_batch is differentiable with respect to the state).
-    _UNROLL = None
-
     def unrolled_training_step(self, windows: Dict[str, Tensor], n_steps: int, through_state: bool = True,
                                is_training: bool = True) -> Tuple[Tensor, Tensor]:
         """Not in the reference, which trains on single steps only: the loss of an ``n_steps`` rollout unrolled under autograd, the
@@ -289,23 +393,23 @@ class AbstractSystemModel(nn.Module):
         the batched graph, bit for bit.
         Out of scope: HIP-graph capture of the unrolled step; the data-parallel trainer (parallel.Trainer.step keeps its single-step
         loss; this method returns an ordinary loss for any optimiser); activation checkpointing; meshes that differ within a batch."""
-        state_name, old_name, d, ca, cp, free_types, per_step, fallback_name, differentiable = self._UNROLL
+        ls = self._LOCKSTEP
         n_steps = int(n_steps)
-        if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (state_name,) + tuple(per_step)):
+        if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (ls.state,) + ls.per_step):
             raise ValueError(f'unrolled_training_step: n_steps = {n_steps} needs windows of at least that many frames (and n_steps >= 1)')
-        if through_state and n_steps > 1 and (self._rmp or not differentiable):
+        if through_state and n_steps > 1 and (self._rmp or not ls.differentiable):
             raise _lib.HgnError('unrolled_training_step: through_state=True differentiates build_graph_batch and expand_graph_batch with '
                                 'respect to the state, which PlateModel and models with a connector cannot do; pass through_state=False '
                                 '(push-forward: the state is detached between the steps)')
         cells, mesh_pos = self._shared_mesh(windows)
         node_type = windows['node_type'][:, 0].to(device).to(torch.int64)
         W, N = node_type.shape[0], node_type.shape[1]
-        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type, state_name: windows[state_name][:, 0].to(device)}
-        if old_name is not None:
-            frame[old_name] = windows[old_name][:, 0].to(device)
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type, ls.state: windows[ls.state][:, 0].to(device)}
+        if ls.prev:
+            frame[ls.prev] = windows[ls.prev][:, 0].to(device)
         losses = []
         for t in range(n_steps):
-            for name in per_step:
+            for name in ls.per_step:
                 frame[name] = windows[name][:, t].to(device)
             accumulate = bool(is_training) and t == 0
             graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate)
@@ -314,14 +418,14 @@ class AbstractSystemModel(nn.Module):
             losses.append(_masked_mse(self.get_target(flat, accumulate), output, self._loss_mask(flat)))
             if t + 1 == n_steps:
                 break
-            cur = flat[state_name]
-            nxt, _ = features.advance_state(output, self._output_normalizer, cur, d, ca, flat[old_name] if old_name else None, cp,
-                                            flat['node_type'], free_types, flat[fallback_name] if fallback_name else None)
+            cur = flat[ls.state]
+            nxt, _ = features.advance_state(output, self._output_normalizer, cur, ls.d, ls.ca, flat[ls.prev] if ls.prev else None,
+                                            ls.cp, flat['node_type'], ls.free_types, flat[ls.fallback] if ls.fallback else None)
             if not through_state:
                 nxt, cur = nxt.detach(), cur.detach()
-            frame[state_name] = nxt.reshape(W, N, d)
-            if old_name is not None:
-                frame[old_name] = cur.reshape(W, N, d)
+            frame[ls.state] = nxt.reshape(W, N, ls.d)
+            if ls.prev:
+                frame[ls.prev] = cur.reshape(W, N, ls.d)
         per_step_losses = torch.stack(losses)
         return per_step_losses.mean(), per_step_losses.detach()
 
@@ -361,33 +465,16 @@ class FlagModel(AbstractSystemModel):
     """src/model/flag.py:17-260."""
     _model_type = 'flag'
     _TYPE_MAP = (0,) + (1,) * 9                  # flag.py:72: class = (node_type != NORMAL)
-    _UNROLL = ('world_pos', 'prev|world_pos', 3, 2.0, -1.0, (NodeType.NORMAL.value,), ('target|world_pos',), None, True)
+    _LOCKSTEP = LockStep(state='world_pos', prev='prev|world_pos', d=3, ca=2.0, cp=-1.0, free_types=(NodeType.NORMAL.value,),
+                         per_step=('target|world_pos',), fallback=None, differentiable=True, expand_steps=399,      # 399: flag.py:236
+                         record_before=True, inv_from=None, errors='world_pos', target='target|world_pos')
 
     def __init__(self, params):
         super().__init__(params, node_size=5, edge_size=7)
 
     def build_graph(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
         """flag.py:65-128."""
-        world_pos = inputs['world_pos'].to(device)
-        prev_world_pos = inputs['prev|world_pos'].to(device)
-        mesh_pos = inputs['mesh_pos'].to(device)
-        node_type = inputs['node_type'].to(device)
-        num_nodes = node_type.shape[0]
-        # velocity (3) | one-hot(type != NORMAL) (2)                                              flag.py:68-74
-        node_features = features.node_features(world_pos, prev_world_pos, node_type, self._TYPE_MAP, 2)
-        senders, receivers = self._mesh_edges(inputs['cells'])
-        edge_features, length = features.rel_edge_features(world_pos, mesh_pos, senders, receivers, want_len=True)
-        mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
-                             receivers=receivers, senders=senders)
-        # max - min incident edge length per node: both aggregates in one pass                      flag.py:100-115
-        csr = topology.segment_csr(receivers, num_nodes, world_pos.device)
-        mm = ops.aggregate([_value(length).unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
-        node_dynamic = self._node_dynamic_normalizer(features.lincomb3(mm[:, 0], 1.0, mm[:, 1], -1.0))
-        return MultiGraphWithPos(
-            node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
-            target_feature=world_pos, mesh_features=mesh_pos, model_type=self._model_type, node_dynamic=node_dynamic,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
-            obstacle_nodes=None)
+        return self._build(inputs, is_training, batched=False)
 
     def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
         """Not in the reference (which builds one graph per frame in Python and concatenates them with
@@ -396,19 +483,19 @@ class FlagModel(AbstractSystemModel):
         handful of launches a single frame takes (node ids of frame b are offset by b*N, as batching.batch_graphs does).
         Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the
         whole batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
-        world_pos = inputs['world_pos'].to(device)
-        B, N = world_pos.shape[0], world_pos.shape[1]
-        prev = inputs['prev|world_pos'].to(device).reshape(B * N, 3)
-        mesh_pos = inputs['mesh_pos'].to(device)
-        mesh_pos = (mesh_pos if mesh_pos.dim() == 3 else mesh_pos.unsqueeze(0).expand(B, N, -1)).reshape(B * N, -1).contiguous()
-        node_type = inputs['node_type'].to(device).reshape(B * N, -1)
-        world_pos = world_pos.reshape(B * N, 3)
-        senders, receivers = self._union_mesh_edges(*self._mesh_edges(inputs['cells']), B, N)
-        node_features = features.node_features(world_pos, prev, node_type, self._TYPE_MAP, 2)
+        return self._build(inputs, is_training, batched=True)
+
+    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
+        rows, B, N = self._frame_rows(inputs, ('world_pos', 'prev|world_pos', 'node_type'), batched)
+        world_pos, mesh_pos = rows['world_pos'], rows['mesh_pos']
+        # velocity (3) | one-hot(type != NORMAL) (2)                                              flag.py:68-74
+        node_features = features.node_features(world_pos, rows['prev|world_pos'], rows['node_type'], self._TYPE_MAP, 2)
+        (senders, receivers), _ = self._frame_edges(inputs['cells'], B, N)
         edge_features, length = features.rel_edge_features(world_pos, mesh_pos, senders, receivers, want_len=True)
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
                              receivers=receivers, senders=senders)
-        csr = topology.segment_csr(receivers, B * N, world_pos.device)
+        # max - min incident edge length per node: both aggregates in one pass                      flag.py:100-115
+        csr = topology.segment_csr(receivers, world_pos.shape[0], world_pos.device)
         mm = ops.aggregate([_value(length).unsqueeze(1)], [(csr.perm, csr.rowptr, csr.seg)], ('max', 'min'))
         node_dynamic = self._node_dynamic_normalizer(features.lincomb3(mm[:, 0], 1.0, mm[:, 1], -1.0))
         return MultiGraphWithPos(
@@ -416,26 +503,6 @@ class FlagModel(AbstractSystemModel):
             target_feature=world_pos, mesh_features=mesh_pos, model_type=self._model_type, node_dynamic=node_dynamic,
             unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             obstacle_nodes=None)
-
-    def _loss_mask(self, data_frame):
-        return torch.eq(data_frame['node_type'].to(device)[:, 0], NodeType.NORMAL.value)
-
-    def training_step(self, graph, data_frame):
-        """flag.py:146-154."""
-        network_output = self(graph)
-        target_normalized = self.get_target(data_frame)
-        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
-
-    @torch.no_grad()
-    def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
-        """flag.py:156-167."""
-        prediction = self(graph)
-        target_normalized = self.get_target(data_frame, False)
-        mask = self._loss_mask(data_frame)
-        acc_loss = _masked_mse(target_normalized, prediction, mask).item()
-        predicted_position = self.update(data_frame, prediction)
-        pos_error = _masked_mse(data_frame['target|world_pos'].to(device), predicted_position, mask).item()
-        return acc_loss, pos_error
 
     def update(self, inputs: Dict, per_node_network_output: Tensor) -> Tensor:
         """flag.py:169-180: next position = 2 cur + acceleration - prev."""
@@ -465,34 +532,12 @@ class FlagModel(AbstractSystemModel):
         return {'faces': trajectory['cells'], 'mesh_pos': trajectory['mesh_pos'], 'gt_pos': trajectory['world_pos'],
                 'pred_pos': predictions}, errors
 
-    @torch.no_grad()
-    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int) -> Tuple[Dict[str, Tensor], Tensor]:
-        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `world_pos`, `prev|world_pos`, `node_type` are
-        [W, T, N, .] (window w may be a view of a longer trajectory); `cells` and a `mesh_pos` shared by all windows are given once.
-        The W windows advance in lock step: every step is one build_graph_batch over the W current states (is_training=False),
-        expand_graph_batch, the network, and one features.rollout_advance launch that integrates, keeps the HANDLE nodes and writes
-        the state BEFORE the step into its slice of the recorded [steps, W, N, 3] slab.  -> what `rollout` returns per window:
-        `pred_pos` [W, steps, N, 3], errors [W, steps].  As in `rollout`, the node-dynamic normaliser accumulates on every build
-        (flag.py:115), here once per step with the statistics of the W frames."""
-        if num_steps is None:
-            num_steps = windows['world_pos'].shape[1]
-        cells, mesh_pos = self._shared_mesh(windows)
-        cur, prev = self._window_start(windows, 'world_pos'), self._window_start(windows, 'prev|world_pos')
-        node_type = self._window_start(windows, 'node_type').to(torch.int64)
-        W, N = cur.shape[0], cur.shape[1]
-        slab = torch.empty(num_steps, W, N, 3, dtype=torch.float32, device=cur.device)
-        nxt, prev_nxt = torch.empty_like(cur), torch.empty_like(prev)
-        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
-        for step in range(num_steps):
-            frame['world_pos'], frame['prev|world_pos'] = cur, prev
-            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, 399, is_training=False)
-            features.rollout_advance(self(graph), self._output_normalizer, cur.view(W * N, 3), 3, 2.0, prev.view(W * N, 3), -1.0,
-                                     node_type.view(W * N, -1), (NodeType.NORMAL.value,), None, nxt.view(W * N, 3),
-                                     rec=slab[step].view(W * N, 3), rec_before=True, prev_out=prev_nxt.view(W * N, 3))
-            cur, nxt, prev, prev_nxt = nxt, cur, prev_nxt, prev
+    def _rollout_result(self, windows, node_type, pred_pos):
+        """rollout_batch: HANDLE nodes keep their position, the state BEFORE the step is recorded and the old state goes into the
+        swap buffer; no extra records.  As in `rollout`, the node-dynamic normaliser accumulates on every build (flag.py:115), here
+        once per step with the statistics of the W frames.  -> `pred_pos` [W, steps, N, 3]."""
         self._visualized = False
-        return {'faces': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'gt_pos': windows['world_pos'],
-                'pred_pos': slab.transpose(0, 1)}, self._batch_errors(windows, 'world_pos', slab)
+        return {'faces': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'gt_pos': windows['world_pos'], 'pred_pos': pred_pos}
 
     @torch.no_grad()
     def _step_fn(self, initial_state, prev_pos, cur_pos, trajectory, mask, step):
@@ -509,26 +554,16 @@ class CylinderModel(AbstractSystemModel):
     """src/model/cylinder.py:17-240 (its remote edges use the 'plate' feature rule, cylinder.py:34)."""
     _model_type = 'plate'
     _TYPE_MAP = (0, -1, -1, -1, 1, 2, 3)        # cylinder.py:71-74: INFLOW->1, OUTFLOW->2, WALL_BOUNDARY->3
-    _UNROLL = ('velocity', None, 2, 1.0, 0.0, (NodeType.NORMAL.value, NodeType.OUTFLOW.value), ('target|velocity', 'pressure'), None, True)
+    _LOCKSTEP = LockStep(state='velocity', prev=None, d=2, ca=1.0, cp=0.0, free_types=(NodeType.NORMAL.value, NodeType.OUTFLOW.value),
+                         per_step=('target|velocity', 'pressure'), fallback=None, differentiable=True, expand_steps=598,  # 598: cylinder.py:218
+                         record_before=False, inv_from=2, errors='velocity', target='target|velocity')
 
     def __init__(self, params):
         super().__init__(params, node_size=6, edge_size=3)
 
     def build_graph(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
         """cylinder.py:65-106."""
-        velocity = inputs['velocity'].to(device)
-        mesh_pos = inputs['mesh_pos'].to(device)
-        node_type = inputs['node_type'].to(device)
-        node_features = features.node_features(velocity, None, node_type, self._TYPE_MAP, 4)
-        senders, receivers = self._mesh_edges(inputs['cells'])
-        edge_features, _ = features.rel_edge_features(mesh_pos, None, senders, receivers)
-        mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
-                             receivers=receivers, senders=senders)
-        return MultiGraphWithPos(
-            node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges],
-            mesh_features=mesh_pos, target_feature=velocity, model_type=self._model_type,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
-            node_dynamic=[], obstacle_nodes=None)
+        return self._build(inputs, is_training, batched=False)
 
     def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
         """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames
@@ -538,13 +573,13 @@ class CylinderModel(AbstractSystemModel):
         `velocity` exactly as build_graph is.
         Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
         batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
-        velocity = inputs['velocity'].to(device)
-        B, N = velocity.shape[0], velocity.shape[1]
-        velocity = velocity.reshape(B * N, -1)
-        mesh_pos = self._union_rows(inputs, 'mesh_pos', B, N)
-        node_type = inputs['node_type'].to(device).reshape(B * N, -1)
-        node_features = features.node_features(velocity, None, node_type, self._TYPE_MAP, 4)
-        senders, receivers = self._union_mesh_edges(*self._mesh_edges(inputs['cells']), B, N)
+        return self._build(inputs, is_training, batched=True)
+
+    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
+        rows, B, N = self._frame_rows(inputs, ('velocity', 'node_type'), batched)
+        velocity, mesh_pos = rows['velocity'], rows['mesh_pos']
+        node_features = features.node_features(velocity, None, rows['node_type'], self._TYPE_MAP, 4)
+        (senders, receivers), _ = self._frame_edges(inputs['cells'], B, N)
         edge_features, _ = features.rel_edge_features(mesh_pos, None, senders, receivers)
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(edge_features, is_training),
                              receivers=receivers, senders=senders)
@@ -553,27 +588,6 @@ class CylinderModel(AbstractSystemModel):
             mesh_features=mesh_pos, target_feature=velocity, model_type=self._model_type,
             unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(edge_features), receivers=receivers, senders=senders),
             node_dynamic=[], obstacle_nodes=None)
-
-    def _loss_mask(self, data_frame):
-        t = data_frame['node_type'].to(device)[:, 0]
-        return torch.logical_or(torch.eq(t, NodeType.OUTFLOW.value), torch.eq(t, NodeType.NORMAL.value))
-
-    def training_step(self, graph, data_frame):
-        """cylinder.py:123-136."""
-        network_output = self(graph)
-        target_normalized = self.get_target(data_frame)
-        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
-
-    @torch.no_grad()
-    def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
-        """cylinder.py:138-153."""
-        prediction = self(graph)
-        target_normalized = self.get_target(data_frame, False)
-        mask = self._loss_mask(data_frame)
-        vel_loss = _masked_mse(target_normalized, prediction, mask).item()
-        velocity_update, _ = self.update(data_frame, prediction)
-        pos_error = _masked_mse(data_frame['target|velocity'].to(device), velocity_update, mask).item()
-        return vel_loss, pos_error
 
     def update(self, inputs: Dict, per_node_network_output: Tensor):
         """cylinder.py:155-165."""
@@ -600,34 +614,18 @@ class CylinderModel(AbstractSystemModel):
         return {'faces': trajectory['cells'], 'mesh_pos': trajectory['mesh_pos'], 'gt_velocity': trajectory['velocity'],
                 'gt_pressure': trajectory['pressure'], 'pred_pressure': torch.stack(pressures), 'pred_velocity': pred_velocity}, errors
 
-    @torch.no_grad()
     def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int):
-        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `velocity`, `node_type` are [W, T, N, .]; `cells` and
-        a `mesh_pos` shared by all windows are given once.  Like `rollout`, it runs the whole window length T whatever `num_steps`
-        says (cylinder.py:178).  Every step is one build_graph_batch over the W current states (is_training=False),
-        expand_graph_batch, the network, and one features.rollout_advance launch that integrates the NORMAL and OUTFLOW nodes and
-        writes the state AFTER the step and the predicted pressure into their slices of the recorded [T, W, N, .] slabs.
-        -> what `rollout` returns per window: `pred_velocity` [W, T, N, 2], `pred_pressure` [W, T, N, 1], errors [W, T]."""
-        num_steps = windows['velocity'].shape[1]
-        cells, mesh_pos = self._shared_mesh(windows)
-        velocity = self._window_start(windows, 'velocity')
-        node_type = self._window_start(windows, 'node_type').to(torch.int64)
-        W, N = velocity.shape[0], velocity.shape[1]
-        slab = torch.empty(num_steps, W, N, 2, dtype=torch.float32, device=velocity.device)
-        pressures = torch.empty(num_steps, W, N, 1, dtype=torch.float32, device=velocity.device)
-        nxt = torch.empty_like(velocity)
-        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
-        for step in range(num_steps):
-            frame['velocity'] = velocity
-            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, 598, is_training=False)
-            features.rollout_advance(self(graph), self._output_normalizer, velocity.view(W * N, 2), 2, 1.0, None, 0.0,
-                                     node_type.view(W * N, -1), (NodeType.NORMAL.value, NodeType.OUTFLOW.value), None,
-                                     nxt.view(W * N, 2), rec=slab[step].view(W * N, 2), inv_out=pressures[step].view(W * N, 1),
-                                     inv_from=2)
-            velocity, nxt = nxt, velocity
+        """The lock-step rollout of the base class.  Like `rollout`, it runs the whole window length T whatever `num_steps` says
+        (cylinder.py:178); the NORMAL and OUTFLOW nodes are integrated, the state AFTER the step and the predicted pressure are
+        recorded.  -> `pred_velocity` [W, T, N, 2], `pred_pressure` [W, T, N, 1], errors [W, T]."""
+        return super().rollout_batch(windows, None)
+
+    def _rollout_records(self, empty):
+        return {'inv_out': empty(1)}                                      # the pressure column of the output
+
+    def _rollout_result(self, windows, node_type, pred_velocity, inv_out):
         return {'faces': windows['cells'], 'mesh_pos': windows['mesh_pos'], 'gt_velocity': windows['velocity'],
-                'gt_pressure': windows.get('pressure'), 'pred_pressure': pressures.transpose(0, 1),
-                'pred_velocity': slab.transpose(0, 1)}, self._batch_errors(windows, 'velocity', slab)
+                'gt_pressure': windows.get('pressure'), 'pred_pressure': inv_out, 'pred_velocity': pred_velocity}
 
     @torch.no_grad()
     def _step_fn(self, initial_state, velocity, pressure, trajectory, pressure_trajectory, step, mask):
@@ -647,7 +645,9 @@ class PlateModel(AbstractSystemModel):
     _model_type = 'plate'
     _TYPE_MAP = (0, 1, 2, 2)                     # plate.py:78: HANDLE (3) -> class 2
     _RADIUS = 0.03                               # plate.py:85
-    _UNROLL = ('world_pos', None, 3, 1.0, 0.0, (NodeType.NORMAL.value,), ('target|world_pos',), 'target|world_pos', False)
+    _LOCKSTEP = LockStep(state='world_pos', prev=None, d=3, ca=1.0, cp=0.0, free_types=(NodeType.NORMAL.value,),
+                         per_step=('target|world_pos',), fallback='target|world_pos', differentiable=False, expand_steps=None,
+                         record_before=False, inv_from=0, errors='world_pos', target='target|world_pos')
 
     def __init__(self, params):
         super().__init__(params, node_size=6, edge_size=8, remote_edge_size=8, edge_sets=('mesh_edges', 'world_edges'))
@@ -658,19 +658,36 @@ class PlateModel(AbstractSystemModel):
 
     def build_graph(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
         """plate.py:69-200.  Not differentiable with respect to positions: the world edges are a radius query of them."""
-        world_pos = inputs['world_pos'].to(device)
-        mesh_pos = inputs['mesh_pos'].to(device)
-        target_world_pos = inputs['target|world_pos'].to(device)
-        if _carries_grad(world_pos, mesh_pos, target_world_pos):
-            raise _lib.HgnError('PlateModel.build_graph is not differentiable with respect to positions (its world edges are a radius '
-                                'query of world_pos); pass tensors that do not require grad, or call it under torch.no_grad()')
-        node_type = inputs['node_type'].to(device)
-        num_nodes = node_type.shape[0]
-        senders, receivers = self._mesh_edges(inputs['cells'], deform=True)
-        # world edges: obstacle -> normal pairs closer than the radius that are not mesh edges          plate.py:84-110
-        nbr_rowptr = self._mesh_neighbours(senders, receivers, num_nodes, world_pos.device)
-        world_senders, world_receivers = features.radius_edges(world_pos, node_type, self._RADIUS, NodeType.OBSTACLE.value,
-                                                                NodeType.NORMAL.value, nbr_rowptr, self._nbr)
+        return self._build(inputs, is_training, batched=False)
+
+    def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
+        """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames
+        of ONE mesh -- `world_pos`, `target|world_pos`, `node_type` with a leading batch dimension [B, N, .], `mesh_pos` [N, 3] or
+        [B, N, 3], `cells` [F, 4] -- become the disjoint union of B graphs (node ids of frame b are offset by b*N, as
+        batching.batch_graphs does); the fields are those build_graph fills, `obstacle_nodes` is [B*N].  The `world_edges` of all
+        frames come from ONE radius query over the union (features.radius_edges_batch with the cached neighbour CSR of the one
+        mesh): one host synchronisation for the batch instead of one per frame, and no pair crosses a frame.  Like build_graph,
+        not differentiable with respect to positions.
+        Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
+        batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
+        return self._build(inputs, is_training, batched=True)
+
+    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
+        if _carries_grad(inputs['world_pos'], inputs['mesh_pos'], inputs['target|world_pos']):
+            raise _lib.HgnError(f"PlateModel.{'build_graph_batch' if batched else 'build_graph'} is not differentiable with respect to "
+                                'positions (its world edges are a radius query of world_pos); pass tensors that do not require grad, '
+                                'or call it under torch.no_grad()')
+        rows, B, N = self._frame_rows(inputs, ('world_pos', 'target|world_pos', 'node_type'), batched)
+        world_pos, mesh_pos, node_type = rows['world_pos'], rows['mesh_pos'], rows['node_type']
+        (senders, receivers), mesh = self._frame_edges(inputs['cells'], B, N, deform=True)
+        # world edges: obstacle -> normal pairs closer than the radius that are not mesh edges (excluded through the neighbour CSR of
+        # the ONE mesh, on local ids); a batch takes all its frames in one query                          plate.py:84-110
+        nbr_rowptr = self._mesh_neighbours(*mesh, N, world_pos.device)
+        query = (self._RADIUS, NodeType.OBSTACLE.value, NodeType.NORMAL.value, nbr_rowptr, self._nbr)
+        if batched:
+            world_senders, world_receivers, _ = features.radius_edges_batch(world_pos, node_type, B, *query)
+        else:
+            world_senders, world_receivers = features.radius_edges(world_pos, node_type, *query)
         world_edge_features, _ = features.rel_edge_features(world_pos, None, world_senders, world_receivers)
         world_edges = EdgeSet(name='world_edges', features=self._world_edge_normalizer(world_edge_features, is_training),
                               receivers=world_receivers, senders=world_senders)
@@ -678,7 +695,7 @@ class PlateModel(AbstractSystemModel):
         mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(mesh_edge_features, is_training),
                              receivers=receivers, senders=senders)
         # one-hot(3) | velocity of the kinematic (obstacle) nodes, zero elsewhere                      plate.py:186-195
-        node_features = features.node_features(target_world_pos, world_pos, node_type, self._TYPE_MAP, 3, vel_first=False,
+        node_features = features.node_features(rows['target|world_pos'], world_pos, node_type, self._TYPE_MAP, 3, vel_first=False,
                                                vel_mask_type=NodeType.OBSTACLE.value)
         obstacle_nodes = torch.eq(node_type[:, 0], NodeType.OBSTACLE.value)
         return MultiGraphWithPos(
@@ -692,73 +709,10 @@ class PlateModel(AbstractSystemModel):
         """Neighbour CSR of ONE mesh for the radius query: -> rowptr; `self._nbr` = the senders of every node's incoming edges,
         cached while the same mesh edges come in."""
         csr = topology.segment_csr(receivers, num_nodes, dev)                      # neighbours of n = senders of its edges
-        if getattr(self, '_nbr_key', None) is not senders:
+        if self._nbr_key is not senders:
             self._nbr = senders[csr.perm.long()].to(torch.int32).contiguous()
             self._nbr_key = senders
         return csr.rowptr
-
-    def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
-        """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames
-        of ONE mesh -- `world_pos`, `target|world_pos`, `node_type` with a leading batch dimension [B, N, .], `mesh_pos` [N, 3] or
-        [B, N, 3], `cells` [F, 4] -- become the disjoint union of B graphs (node ids of frame b are offset by b*N, as
-        batching.batch_graphs does); the fields are those build_graph fills, `obstacle_nodes` is [B*N].  The `world_edges` of all
-        frames come from ONE radius query over the union (features.radius_edges_batch with the cached neighbour CSR of the one
-        mesh): one host synchronisation for the batch instead of one per frame, and no pair crosses a frame.  Like build_graph,
-        not differentiable with respect to positions.
-        Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
-        batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
-        world_pos = inputs['world_pos'].to(device)
-        mesh_pos = inputs['mesh_pos'].to(device)
-        target_world_pos = inputs['target|world_pos'].to(device)
-        if _carries_grad(world_pos, mesh_pos, target_world_pos):
-            raise _lib.HgnError('PlateModel.build_graph_batch is not differentiable with respect to positions (its world edges are a '
-                                'radius query of world_pos); pass tensors that do not require grad, or call it under torch.no_grad()')
-        B, N = world_pos.shape[0], world_pos.shape[1]
-        world_pos = world_pos.reshape(B * N, 3)
-        target_world_pos = target_world_pos.reshape(B * N, 3)
-        mesh_pos = self._union_rows(inputs, 'mesh_pos', B, N)
-        node_type = inputs['node_type'].to(device).reshape(B * N, -1)
-        senders1, receivers1 = self._mesh_edges(inputs['cells'], deform=True)
-        senders, receivers = self._union_mesh_edges(senders1, receivers1, B, N)
-        # world edges of all frames in one query; mesh neighbours are excluded through the CSR of the ONE mesh   plate.py:84-110
-        nbr_rowptr = self._mesh_neighbours(senders1, receivers1, N, world_pos.device)
-        world_senders, world_receivers, _ = features.radius_edges_batch(
-            world_pos, node_type, B, self._RADIUS, NodeType.OBSTACLE.value, NodeType.NORMAL.value, nbr_rowptr, self._nbr)
-        world_edge_features, _ = features.rel_edge_features(world_pos, None, world_senders, world_receivers)
-        world_edges = EdgeSet(name='world_edges', features=self._world_edge_normalizer(world_edge_features, is_training),
-                              receivers=world_receivers, senders=world_senders)
-        mesh_edge_features, _ = features.rel_edge_features(world_pos, mesh_pos, senders, receivers)
-        mesh_edges = EdgeSet(name='mesh_edges', features=self._mesh_edge_normalizer(mesh_edge_features, is_training),
-                             receivers=receivers, senders=senders)
-        node_features = features.node_features(target_world_pos, world_pos, node_type, self._TYPE_MAP, 3, vel_first=False,
-                                               vel_mask_type=NodeType.OBSTACLE.value)
-        obstacle_nodes = torch.eq(node_type[:, 0], NodeType.OBSTACLE.value)
-        return MultiGraphWithPos(
-            node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges, world_edges],
-            mesh_features=mesh_pos, target_feature=world_pos, model_type=self._model_type,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=mesh_edge_features, receivers=receivers,
-                                       senders=senders),
-            node_dynamic=None, obstacle_nodes=obstacle_nodes)
-
-    def _loss_mask(self, data_frame):
-        return torch.eq(data_frame['node_type'].to(device)[:, 0], NodeType.NORMAL.value)
-
-    def training_step(self, graph, data_frame):
-        """plate.py:218-228."""
-        network_output = self(graph)
-        target_normalized = self.get_target(data_frame)
-        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
-
-    @torch.no_grad()
-    def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
-        """plate.py:230-244."""
-        prediction = self(graph)
-        target_normalized = self.get_target(data_frame, False)
-        mask = self._loss_mask(data_frame)
-        vel_loss = _masked_mse(target_normalized, prediction, mask).item()
-        predicted_position, _, _ = self.update(data_frame, prediction)
-        pos_error = _masked_mse(data_frame['target|world_pos'].to(device), predicted_position, mask).item()
-        return vel_loss, pos_error
 
     def update(self, inputs: Dict, per_node_network_output: Tensor):
         """plate.py:246-257: next position = current + predicted velocity."""
@@ -792,39 +746,17 @@ class PlateModel(AbstractSystemModel):
                 'mask': torch.eq(start['node_type'][:, 0], NodeType.OBSTACLE.value), 'gt_pos': trajectory['world_pos'],
                 'pred_pos': pred_pos, 'cur_positions': torch.stack(positions), 'cur_velocities': torch.stack(velocities)}, errors
 
-    @torch.no_grad()
-    def rollout_batch(self, windows: Dict[str, Tensor], num_steps: int):
-        """Not in the reference: `rollout` for W windows of ONE mesh at once.  `world_pos`, `target|world_pos`, `node_type` are
-        [W, T, N, .]; `cells` and a `mesh_pos` shared by all windows are given once.  Every step is one build_graph_batch over the W
-        current states (is_training=False; one radius query for all windows), expand_graph_batch, the network, and one
-        features.rollout_advance launch that moves the NORMAL nodes by the predicted velocity, puts the scripted nodes on
-        `target|world_pos[w, t]` and writes the new position, the position before the step and the velocity into their slices of the
-        recorded [steps, W, N, 3] slabs.  -> what `rollout` returns per window: `pred_pos`, `cur_positions`, `cur_velocities`
-        [W, steps, N, 3], `mask` [W, N], errors [W, steps]."""
-        if num_steps is None:
-            num_steps = windows['world_pos'].shape[1]
-        cells, mesh_pos = self._shared_mesh(windows)
-        position = self._window_start(windows, 'world_pos')
-        node_type = self._window_start(windows, 'node_type').to(torch.int64)
-        W, N = position.shape[0], position.shape[1]
-        scripted = windows['target|world_pos'][:, :num_steps].to(device).transpose(0, 1).contiguous()       # [steps, W, N, 3], once
-        slab, before, velocities = (torch.empty(num_steps, W, N, 3, dtype=torch.float32, device=position.device) for _ in range(3))
-        nxt = torch.empty_like(position)
-        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type}
-        for step in range(num_steps):
-            frame['world_pos'], frame['target|world_pos'] = position, scripted[step]
-            graph = self.expand_graph_batch(self.build_graph_batch(frame, is_training=False), W, step, num_steps, is_training=False)
-            features.rollout_advance(self(graph), self._output_normalizer, position.view(W * N, 3), 3, 1.0, None, 0.0,
-                                     node_type.view(W * N, -1), (NodeType.NORMAL.value,), scripted[step].view(W * N, 3),
-                                     nxt.view(W * N, 3), rec=slab[step].view(W * N, 3), prev_out=before[step].view(W * N, 3),
-                                     inv_out=velocities[step].view(W * N, 3), inv_from=0)
-            position, nxt = nxt, position
-        cells_all = windows['cells']
-        triangles = torch.cat((cells_all[..., 0:3], cells_all[..., [2, 3, 0]]), dim=-2)                 # plate.py:289-297
+    def _rollout_records(self, empty):
+        return {'prev_out': empty(3), 'inv_out': empty(3)}               # the position before the step; the predicted velocity
+
+    def _rollout_result(self, windows, node_type, pred_pos, prev_out, inv_out):
+        """rollout_batch: the NORMAL nodes move by the predicted velocity, the scripted ones are put on `target|world_pos[w, t]`.
+        -> `pred_pos`, `cur_positions`, `cur_velocities` [W, steps, N, 3], `mask` [W, N]."""
+        cells = windows['cells']
+        triangles = torch.cat((cells[..., 0:3], cells[..., [2, 3, 0]]), dim=-2)                         # plate.py:289-297
         return {'faces': triangles, 'mesh_pos': windows['mesh_pos'],
                 'mask': torch.eq(node_type[:, :, 0], NodeType.OBSTACLE.value), 'gt_pos': windows['world_pos'],
-                'pred_pos': slab.transpose(0, 1), 'cur_positions': before.transpose(0, 1),
-                'cur_velocities': velocities.transpose(0, 1)}, self._batch_errors(windows, 'world_pos', slab)
+                'pred_pos': pred_pos, 'cur_positions': prev_out, 'cur_velocities': inv_out}
 
     @torch.no_grad()
     def _step_fn(self, initial_state, cur_pos, trajectory, cur_positions, cur_velocities, target_world_pos, step, mask,

@@ -469,3 +469,85 @@ def test_batched_calls_refuse_what_they_cannot_do():
     with pytest.raises(_lib.HgnError, match='expand_graph_batch.*not differentiable'):
         hyper.expand_graph_batch(g, 2, 0, 5, False)
     assert hyper._remote_graph._clusters is None             # refused before any clustering
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# one body behind build_graph and build_graph_batch; run-time caches
+# ----------------------------------------------------------------------------------------------------------------
+ACCUMULATORS = ('_acc_sum', '_acc_sum_squared', '_acc_count', '_num_accumulations')
+
+
+def same(x, y):
+    """Two graph fields: tensors by torch.equal, EdgeSets field by field, lists element by element, the rest by ==."""
+    if torch.is_tensor(x) or torch.is_tensor(y):
+        return torch.is_tensor(x) and torch.is_tensor(y) and x.shape == y.shape and torch.equal(x, y)
+    if isinstance(x, (list, tuple)) and not hasattr(x, '_fields'):
+        return type(x) is type(y) and len(x) == len(y) and all(same(a, b) for a, b in zip(x, y))
+    if hasattr(x, '_fields'):
+        return type(x) is type(y) and all(same(getattr(x, f), getattr(y, f)) for f in x._fields)
+    return x == y
+
+
+def assert_same_graph(got, ref):
+    assert_same_sets(got, ref)
+    for field in ('target_feature', 'mesh_features', 'unnormalized_edges', 'node_dynamic', 'obstacle_nodes', 'model_type'):
+        assert same(getattr(got, field), getattr(ref, field)), field
+
+
+def leading_one(frame):
+    return {k: (v if k == 'cells' else v.unsqueeze(0)) for k, v in cuda_frame(frame).items()}
+
+
+ONE_FRAME_CASES = [('flag', 0, None), ('cylinder', 0, None), ('plate', 0, True), ('plate', 2, False)]
+
+
+@pytest.mark.parametrize('kind,index,world', ONE_FRAME_CASES, ids=['flag', 'cylinder', 'plate-world-edges', 'plate-no-world-edge'])
+def test_a_batch_of_one_frame_is_that_frame(kind, index, world):
+    """12. build_graph_batch of one frame with a leading dimension of 1 == build_graph of that frame: every field, and after an
+    accumulating build every accumulator of every normaliser, bit for bit (the same kernels over the same rows)."""
+    from hgn_amd.normalizer import Normalizer
+    a, b, frames = model_pair(kind)
+    frame = frames[index]
+    for is_training in (False, True):
+        one = a.build_graph(cuda_frame(frame), is_training)
+        got = b.build_graph_batch(leading_one(frame), is_training)
+        assert_same_graph(got, one)
+        if world is not None:
+            count = one.edge_sets[1].senders.shape[0]
+            assert count >= 1 if world else count == 0
+    na = {n: m for n, m in a.named_modules() if isinstance(m, Normalizer)}
+    nb = {n: m for n, m in b.named_modules() if isinstance(m, Normalizer)}
+    assert sorted(na) == sorted(nb) and len(na) >= 7
+    for name in na:
+        for acc in ACCUMULATORS:
+            assert torch.equal(getattr(na[name], acc), getattr(nb[name], acc)), (name, acc)
+    assert float(a._node_normalizer._num_accumulations) == 2.0          # the warm-up frame and the accumulating build
+
+
+def test_run_time_caches_do_not_travel_in_copies_and_pickles():
+    """13. After a build_graph and a build_graph_batch a PlateModel holds every topology cache; a deep copy, a pickle round trip
+    and a checkpoint from before the caches existed start without them, hold the same weights and build the same graphs."""
+    import pickle
+    from hgn_amd import system_model
+    model, _, frames = model_pair('plate', network=True)
+    caches = system_model.AbstractSystemModel._RUNTIME_CACHES
+    assert set(caches) == {'_fwd_cache', '_cells_key', '_cells_edges', '_batch_edges_key', '_batch_edges', '_nbr_key', '_nbr'}
+    frame, stacked = cuda_frame(frames[0]), stack(frames[:2])
+    with torch.no_grad():
+        one, union = model.build_graph(frame, False), model.build_graph_batch(stacked, False)
+    assert all(getattr(model, name) is not None for name in caches if name != '_fwd_cache')
+    old_state = copy.deepcopy(model.__getstate__())
+    for name in caches:
+        old_state.pop(name, None)
+    old = system_model.PlateModel.__new__(system_model.PlateModel)
+    old.__setstate__(old_state)
+    assert not any(name in old.__dict__ for name in caches)
+    for twin in (copy.deepcopy(model), pickle.loads(pickle.dumps(model)), old):
+        assert all(getattr(twin, name) is None for name in caches)
+        sd, ref = twin.state_dict(), model.state_dict()
+        assert list(sd) == list(ref) and len(sd) >= 2 and all(torch.equal(sd[k], ref[k]) for k in ref)
+        with torch.no_grad():
+            assert_same_graph(twin.build_graph(frame, False), one)
+            assert_same_graph(twin.build_graph_batch(stacked, False), union)
+        assert all(getattr(twin, name) is not None for name in caches if name != '_fwd_cache')
+    assert all(getattr(model, name) is not None for name in caches if name != '_fwd_cache')      # the live model keeps its own
