@@ -1196,7 +1196,10 @@ class EdgeBlockFn(torch.autograd.Function):
                                'hgn_segment_reduce_bwd')
                 b2.d_out = g_eff.data_ptr()
                 b, fused = b2, True
-        fuse_seg = (not fused and pk_t is not None and E > 0 and topo.r.max_rows <= _FUSED_SEG_MAX_ROWS
+        # (not in 'bf16': the in-kernel sums add a segment that crosses the end of a 64-row tile in two parts, so their last bit depends
+        #  on the row offset of a graph inside its batch; dh and dW1's node columns take dP as an OPERAND, and where the other modes carry
+        #  that bit as 1e-7, a bf16 rounding that it moves is 4e-3 of the element.  The streaming sums below add in one order.)
+        fuse_seg = (not fused and pk_t is not None and E > 0 and topo.r.max_rows <= _FUSED_SEG_MAX_ROWS and c.products() != 1
                     and L.hgn_mlp_bwd6_eligible(C.byref(b)))
         if fuse_seg:
             (dP[:, LAT:] if same else dP[1]).zero_()
