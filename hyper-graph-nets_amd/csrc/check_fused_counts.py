@@ -106,7 +106,9 @@ def check3(text: str) -> None:
 # LDS-DMA of a ring piece -- issued BEFORE them -- must have landed.  Safe exactly when, walking back from the wait, the first N
 # vector-memory instructions are reached without passing a label (another path could join with a different count), are not LDS-DMA,
 # and the kernel has no scratch access (a spill reload is a vector-memory operation nobody counted).
-EDGE_KERNELS = ['_ZN3hgn20mlp6_fwd_edge_kernelILi%dEEEv13hgn_mlp_fwd_t' % n for n in (6, 3)]
+# (<NP, SAVEZ>: with the z1 / z2 row stores, 18 operations stay in flight between two blocks of a full tile; without them the two
+#  sign-word stores)
+EDGE_KERNELS = ['_ZN3hgn20mlp6_fwd_edge_kernelILi%dELb%dEEEv13hgn_mlp_fwd_t' % (n, z) for n in (6, 3) for z in (1, 0)]
 EDGE_KERNEL = EDGE_KERNELS[0]
 _VMEM = ('global_load', 'global_store', 'global_atomic', 'buffer_', 'flat_', 'scratch_')
 
@@ -149,10 +151,12 @@ if __name__ == '__main__':
         if KERNEL3 + ':' in text:
             check3(text)
             print('check_fused_counts: ok (fused backward, two-term fp16 form: 12 phases, counted waits match the emitted instructions)')
+        if EDGE_KERNEL + ':' in text and not all(k + ':' in text for k in EDGE_KERNELS):
+            raise AssertionError('an instantiation of mlp6_fwd_edge_kernel is missing from the listing')
         for kernel in EDGE_KERNELS:
             if kernel + ':' in text:
                 n = check_edge_forward(text, kernel)
-                print(f'check_fused_counts: ok (edge forward {kernel[-30:-25]}: {n} counted waits leave only younger, unconditional operations in flight; no scratch)')
+                print(f'check_fused_counts: ok (edge forward {kernel[30:41]}: {n} counted waits leave only younger, unconditional operations in flight; no scratch)')
     except (AssertionError, ValueError, StopIteration) as e:
         print('check_fused_counts: FAILED:', e, file=sys.stderr)
         sys.exit(1)

@@ -631,7 +631,7 @@ extern "C" int hgn_edge_bwd_fused_workspace_bytes(int64_t M, size_t* bytes) {
 }
 
 extern "C" int hgn_edge_bwd_fused_eligible(const hgn_mlp_bwd_t* a) {
-  if (!a || !hgn_mlp_bwd6_eligible(a)) return 0;          // (includes the HGN_F_FP32_MFMA flag of the call)
+  if (!a || !hgn_mlp_bwd6_eligible(a) || (a->flags & HGN_F_DATA_ONLY)) return 0;          // (includes the HGN_F_FP32_MFMA flag of the call)
   if (a->n_dx != 1 || !a->dx[0].residual || a->dx[0].K != 128 || a->seg_dz1 || !a->dz1) return 0;
   if (a->agg_dout && (a->n_agg_ops != 1 || a->agg_ops[0] != HGN_OP_SUM)) return 0;      // several aggregates (pna): the two-launch path
   const int64_t ldmax = a->ld_dout > a->dx[0].ld ? a->ld_dout : a->dx[0].ld;
@@ -644,6 +644,7 @@ static int edge_bwd_fused_impl(const hgn_mlp_bwd_t* a, const hgn_wfuse_t* w, voi
                                void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!a || !w) return hgn_fail(HGN_E_INVALID, "hgn_edge_bwd_fused: null args");
+  if (a->flags & HGN_F_DATA_ONLY) return hgn_fail(HGN_E_INVALID, "hgn_edge_bwd_fused: HGN_F_DATA_ONLY is served by hgn_mlp_bwd (this kernel forms weight gradients)");
   if (a->M == 0) return HGN_OK;
   size_t need = 0;
   if (a->M < 0 || hgn_edge_bwd_fused_workspace_bytes(a->M, &need) != HGN_OK || !workspace || ws_bytes < need ||

@@ -380,7 +380,9 @@ extern "C" int hgn_mlp_bwd(const hgn_mlp_bwd_t* a, void* stream) {
   // otherwise, as the forward refuses such a residual.  A narrower d_out (decoder) takes the masked scalar loads at any address.
   if (a->d_out && a->out_w == 128 && ((a->ld_dout & 3) || !aligned16(a->d_out)))
     return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: a 128-wide d_out must be 16-byte aligned, ld_dout a multiple of 4");
-  if (a->ln_ws && (!a->ln_g || !a->d_gamma || !a->d_beta)) return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: LayerNorm gradient outputs missing");
+  const bool data_only = (a->flags & HGN_F_DATA_ONLY) != 0;      // no weight gradients: nothing reads dz3 / dz2, no LayerNorm sums
+  if (data_only && (a->dz3 || a->dz2)) return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: HGN_F_DATA_ONLY takes no dz3 / dz2");
+  if (a->ln_ws && (!a->ln_g || (!data_only && (!a->d_gamma || !a->d_beta)))) return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: LayerNorm gradient outputs missing");
   for (int i = 0; i < a->n_dx; ++i)
     if (!a->dx[i].W || !a->dx[i].dx || a->dx[i].K < 1 || (a->dx[i].residual && (a->dx[i].K != 128 || a->out_w != 128)))
       return hgn_fail(HGN_E_INVALID, "hgn_mlp_bwd: bad dx request");
@@ -396,7 +398,7 @@ extern "C" int hgn_mlp_bwd(const hgn_mlp_bwd_t* a, void* stream) {
   } else {
     hipLaunchKernelGGL(mlp_bwd_kernel, dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, b);
   }
-  if (b.ln_ws && !(a->flags & HGN_F_DEFER_LN)) {
+  if (b.ln_ws && !(a->flags & HGN_F_DEFER_LN) && !data_only) {
     // partial slabs live behind the slabs of a 64-row tiling (hgn_mlp_bwd_ln_workspace_bytes), whatever tiling ran
     float* part = b.ln_ws + ln_slab_capacity(a->M) * 256;
     if (launch_ln_reduce(b.ln_ws, tiles, part, a->d_gamma, a->d_beta, a->ln_accumulate, (hipStream_t)stream) != HGN_OK) return HGN_E_LAUNCH;

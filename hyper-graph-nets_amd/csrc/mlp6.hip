@@ -305,7 +305,11 @@ __global__ __launch_bounds__(64 * NWV, NWV != WG / 64 ? 1 : (NS == 1 ? 3 : 2)) v
 // 32-bit VGPR next to a scalar base (no 64-bit vector arithmetic, no per-source loop, no width / alignment cases), the stores of all
 // tiles but the launch's last carry no per-row test, ReLU + sign word cost three instructions per value instead of four and a half.
 // ----------------------------------------------------------------------------------------------------------
-template <int NP>
+// SAVEZ = false: the training forward of an MLP whose weights get no gradient (a.z1 == a.z2 == null).  The saved activation rows are
+// read by weight-gradient kernels only -- the data chain of the backward reads the sign words, x-hat and rstd --, so this form leaves
+// their stores out (1 024 of the 2 084 bytes the kernel writes per row) and never touches a.z1 / a.z2; everything else, the sign words
+// and the in-kernel sums included, is the same code: bit-identical results.
+template <int NP, bool SAVEZ = true>
 __global__ __launch_bounds__(WG, 2) void mlp6_fwd_edge_kernel(const hgn_mlp_fwd_t a) {
   constexpr int NS = 2;
   __shared__ __attribute__((aligned(16))) __bf16 lds[HALF_BF16];
@@ -384,26 +388,30 @@ __global__ __launch_bounds__(WG, 2) void mlp6_fwd_edge_kernel(const hgn_mlp_fwd_
   // Between two blocks: ReLU, sign words, the saved activation rows -- and the wait for the next block's first piece, whose DMA was
   // issued BEFORE these stores.  In a full tile their number is static (per sub-tile 8 row stores + 1 sign-word store): the wait
   // leaves them in flight.  Path by path (no join in between: the compiler's own bookkeeping takes the smaller count at a join).
-  constexpr int SAVE_OPS = NS * (NB + 1);
+  // (SAVEZ = false: the sign-word stores alone.)
+  constexpr int SAVE_OPS = SAVEZ ? NS * (NB + 1) : NS;
   auto save = [&](auto full_, Act (&z)[NS], Act (&next_acc)[NS], float* __restrict__ dst, unsigned word) {
     constexpr bool FULL = decltype(full_)::value;
     const unsigned ln = lane_now();
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
       const unsigned m = relu_with_bits(z[u]);
-      t_store_rows32<FULL>(z[u], dst, row0[u], M, st);
+      if constexpr (SAVEZ) t_store_rows32<FULL>(z[u], dst, row0[u], M, st);
       if (FULL || row_valid(u, ln)) a.relu_bits[row_clamped(u, ln) * 8u + word + (ln >> 4)] = m;
     }
     gemm6q_landed<NS, FULL ? SAVE_OPS : 0>(next_acc, z);
   };
-  if (full) save(std::true_type{}, acc, b, a.z1, 0u); else save(std::false_type{}, acc, b, a.z1, 0u);
+  float* z1 = nullptr;
+  float* z2 = nullptr;
+  if constexpr (SAVEZ) { z1 = a.z1; z2 = a.z2; }
+  if (full) save(std::true_type{}, acc, b, z1, 0u); else save(std::false_type{}, acc, b, z1, 0u);
   gemm6q<NS, NP, true, 0, 0, 0>(b, acc, lds, pk2, pk3, false, [] {}, [&](int q, Act (&free_a)[NS]) {
     if (q == 3) {
 #pragma unroll
       for (int u = 0; u < NS; ++u) t_load(free_a[u], a.b3, kq);
     }
   });
-  if (full) save(std::true_type{}, b, acc, a.z2, 4u); else save(std::false_type{}, b, acc, a.z2, 4u);
+  if (full) save(std::true_type{}, b, acc, z2, 4u); else save(std::false_type{}, b, acc, z2, 4u);
   gemm6q<NS, NP, true, 0, 0, NB>(acc, b, lds, pk3, nullptr, false, [] {
   }, [&](int q, Act (&free_b)[NS]) {                // the residual rows arrive while pieces 2 and 3 multiply, in the registers of the
     if (q == 2) { const unsigned ln = lane_now(); t_load32(free_b[0], a.res, row_clamped(0, ln) * 512u + 16u * (ln >> 4)); }      // operand vectors that
@@ -1304,17 +1312,29 @@ bool cs_eligible(const hgn_mlp_fwd_t* a) {
   return true;
 }
 
-// the arguments of a training edge block as mlp6_fwd_edge_kernel assumes them (everything else: the general kernel)
-static bool edge_block_shape(const hgn_mlp_fwd_t* a) {
-  if ((a->flags & HGN_F_GENERAL_FWD) || a->n_src != 1 || a->n_add != 2 || a->n_post != 0) return false;
+// the arguments of a training edge block as mlp6_fwd_edge_kernel assumes them -> 1: with z1 / z2 (SAVEZ), 2: with neither (the forward
+// of a backward without weight gradients); 0: everything else, one of the two alone included: the general kernel
+static int edge_block_shape(const hgn_mlp_fwd_t* a) {
+  if ((a->flags & HGN_F_GENERAL_FWD) || a->n_src != 1 || a->n_add != 2 || a->n_post != 0) return 0;
   const hgn_src_t& s = a->src[0];
-  if (s.K != 128 || s.idx || s.ld != 128 || !aligned16(s.x)) return false;
-  if (!a->z1 || !a->z2 || !a->xhat || !a->rstd || !a->relu_bits || !a->ln_g || !a->ln_b || !a->res) return false;
-  if (a->ld_out != 128 || a->ld_res != 128 || a->out_w != 128) return false;
-  if (!aligned16(a->z1) || !aligned16(a->z2) || !aligned16(a->xhat) || !aligned16(a->out) || !aligned16(a->res)) return false;
+  if (s.K != 128 || s.idx || s.ld != 128 || !aligned16(s.x)) return 0;
+  if (!a->z1 != !a->z2 || !a->xhat || !a->rstd || !a->relu_bits || !a->ln_g || !a->ln_b || !a->res) return 0;
+  if (a->ld_out != 128 || a->ld_res != 128 || a->out_w != 128) return 0;
+  if (a->z1 && (!aligned16(a->z1) || !aligned16(a->z2))) return 0;
+  if (!aligned16(a->xhat) || !aligned16(a->out) || !aligned16(a->res)) return 0;
   for (int i = 0; i < 2; ++i)
-    if (!a->add[i].P || !a->add[i].idx || (a->add[i].ld & 3) || !aligned16(a->add[i].P)) return false;
-  return (a->M + 2 * TILE_ROWS) * 512 < ((int64_t)1 << 32);      // 32-bit byte offsets into the [M, 128] row arrays
+    if (!a->add[i].P || !a->add[i].idx || (a->add[i].ld & 3) || !aligned16(a->add[i].P)) return 0;
+  if ((a->M + 2 * TILE_ROWS) * 512 >= ((int64_t)1 << 32)) return 0;      // 32-bit byte offsets into the [M, 128] row arrays
+  return a->z1 ? 1 : 2;
+}
+
+// 128-row tiles (two sub-tiles per wave, two workgroups per CU) pay for edge-shaped launches -- one source (+ gathered pre-projections) over
+// >= 98 304 rows --; a node update (several 128-wide sources, a sixth of the rows) is faster on 64-row tiles at three workgroups per CU
+// (mode 3, 204 800 rows: 0.190 -> 0.176 ms, tools/exp_tile64.py).  Same bits either way.
+static bool fwd128(const hgn_mlp_fwd_t* a, int np_) {
+  const bool edge_like = a->n_src == 1 || a->n_add > 0;
+  return (tile128() || (tile128_fwd() && a->M >= big_min_rows() && !(a->flags & HGN_F_TILE64_FWD) && (edge_like || np_ == 6))) && (np_ == 6 || np_ == 3) &&
+         a->M > TILE_ROWS;
 }
 
 int launch_mlp6_fwd(const hgn_mlp_fwd_t* a, void* stream) {
@@ -1351,17 +1371,15 @@ int launch_mlp6_fwd(const hgn_mlp_fwd_t* a, void* stream) {
     else hipLaunchKernelGGL((mlp6_fwd_kernel<1, 6, 4 + LAT_LOADERS>), dim3((unsigned)tiles), dim3(T), 0, (hipStream_t)stream, *a);
     return hgn_check_launch("hgn_mlp_fwd (split-bf16, latency form)");
   }
-  // 128-row tiles (two sub-tiles per wave, two workgroups per CU) pay for edge-shaped launches -- one source (+ gathered pre-projections) over
-  // >= 98 304 rows --; a node update (several 128-wide sources, a sixth of the rows) is faster on 64-row tiles at three workgroups per CU
-  // (mode 3, 204 800 rows: 0.190 -> 0.176 ms, tools/exp_tile64.py).  Same bits either way.
-  const bool edge_like = a->n_src == 1 || a->n_add > 0;
-  if ((tile128() || (tile128_fwd() && a->M >= big_min_rows() && !(a->flags & HGN_F_TILE64_FWD) && (edge_like || np_ == 6))) && (np_ == 6 || np_ == 3) &&
-      a->M > TILE_ROWS) {
+  if (fwd128(a, np_)) {
     const long tiles = (a->M + 2 * TILE_ROWS - 1) / (2 * TILE_ROWS);
+    const int form = edge_block_shape(a);
     if (np_ == 3) {
-      if (edge_block_shape(a)) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<3>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
+      if (form == 1) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<3, true>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
+      else if (form == 2) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<3, false>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
       else hipLaunchKernelGGL((mlp6_fwd_kernel<2, 3>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
-    } else if (edge_block_shape(a)) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<6>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
+    } else if (form == 1) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<6, true>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
+    else if (form == 2) hipLaunchKernelGGL((mlp6_fwd_edge_kernel<6, false>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL((mlp6_fwd_kernel<2, 6>), dim3((unsigned)tiles), dim3(WG), 0, (hipStream_t)stream, *a);
   } else {
     const long tiles = (a->M + TILE_ROWS - 1) / TILE_ROWS;
@@ -1373,6 +1391,16 @@ int launch_mlp6_fwd(const hgn_mlp_fwd_t* a, void* stream) {
   return hgn_check_launch("hgn_mlp_fwd (split-bf16)");
 }
 }  // namespace hgn
+
+// Which kernel hgn_mlp_fwd takes for these arguments, decided as launch_mlp6_fwd decides it (shapes and pointers only; host only).
+extern "C" int hgn_mlp_fwd_edge_form(const hgn_mlp_fwd_t* a) {
+  if (!a || !valid_products(a->products) || !hgn_mlp_fwd6_eligible(a) || a->n_post != 0) return 0;
+#if HGN_LAB
+  if (hgn::g_big_tiles && !hgn::tile128() && a->M >= hgn::big_min_rows()) return 0;
+#endif
+  if (hgn::cs_eligible(a) || (a->M + TILE_ROWS - 1) / TILE_ROWS <= hgn::lat_max_tiles()) return 0;
+  return hgn::fwd128(a, matmul_products(a->products)) ? hgn::edge_block_shape(a) : 0;
+}
 
 namespace hgn {
 // Column-split latency form of the pre-projection (see mlp6_fwd_cs_kernel): 16 rows per workgroup, wave w produces the operand

@@ -621,6 +621,8 @@ extern "C" int hgn_wgrad_workspace_bytes(int64_t M, int n_tasks, size_t* bytes) 
 static int wgrad_impl(const hgn_wtask_t* tasks, int n_tasks, int64_t M, void* workspace, size_t ws_bytes, hgn_wred_task_t* red_out,
                       void* stream) {
   if (n_tasks == 0) return HGN_OK;
+  for (int i = 0; tasks && i < n_tasks && i < HGN_MAX_WTASK; ++i)      // (before anything else of the call is looked at)
+    if (tasks[i].flags & HGN_F_DATA_ONLY) return hgn_fail(HGN_E_INVALID, "hgn_mlp_wgrad: a task carries HGN_F_DATA_ONLY (a backward without weight gradients)");
   size_t need = 0;
   if (!tasks || hgn_wgrad_workspace_bytes(M, n_tasks, &need) != HGN_OK || !workspace || ws_bytes < need)
     return hgn_fail(HGN_E_INVALID, "hgn_mlp_wgrad: bad tasks / workspace too small");

@@ -18,6 +18,7 @@ HGN_MAX_PACK = 32
 NUM_KERNEL_IDS = 15
 OP_CODES = {'sum': 0, 'mean': 1, 'max': 2, 'min': 3, 'std': 4}      # 'std': hgn_segment_reduce5_* only
 F_FP32_MFMA, F_GENERAL_FWD, F_TILE64_FWD, F_DEFER_LN = 1, 2, 4, 8          # hgn_mlp_fwd_t.flags / hgn_mlp_bwd_t.flags / hgn_wtask_t.flags
+F_DATA_ONLY = 16         # hgn_mlp_bwd_t.flags: data gradients only (the MLP's weights get no gradient)
 KERNEL_NAMES = ['mlp_fwd_edge', 'mlp_fwd', 'mlp_bwd_edge', 'mlp_bwd', 'wgrad', 'seg_fwd', 'seg_bwd', 'linear_fwd',
                 'linear_bwd', 'adam', 'csr', 'wgrad_node', 'seg_fwd_agg', 'features', 'edge_bwd_fused']
 
@@ -130,6 +131,7 @@ _SIGS = {
     'hgn_get_matmul_products': (C.c_int, []),
     'hgn_mlp_fwd6_eligible': (C.c_int, [C.POINTER(MlpFwd)]),
     'hgn_mlp_fwd_post_eligible': (C.c_int, [C.POINTER(MlpFwd)]),
+    'hgn_mlp_fwd_edge_form': (C.c_int, [C.POINTER(MlpFwd)]),
     'hgn_linear_fwd6': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64,
                                   C.c_int, C.c_void_p]),
     'hgn_linear_fwd6z': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64,

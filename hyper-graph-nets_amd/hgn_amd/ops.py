@@ -22,9 +22,11 @@ _PRODUCTS = {'fp32': 3, 'fp32-f16x2': 3, 'fp32-bf16x3': 6, 'bf16': 1, 'fp16': 2}
 _ENV = __import__('os').environ
 # Process-wide DEFAULTS, resolved once here (the library itself reads no environment variable): what a Context that does not say
 # otherwise follows.  HGN_FP32_MFMA: the plain fp32-MFMA kernels everywhere; HGN_NO_FUSED_BWD: hgn_mlp_bwd + hgn_mlp_wgrad instead of
-# hgn_edge_bwd_fused; HGN_NO_EDGE_FWD: the general forward kernel for training edge blocks too.
+# hgn_edge_bwd_fused; HGN_NO_EDGE_FWD: the general forward kernel for training edge blocks too; HGN_NO_DATA_ONLY: an MLP whose
+# parameters are frozen still saves z1 / z2 and runs its weight-gradient launches (A/B runs against the data-only backward).
 _DEFAULTS = {'precision': _ENV.get('HGN_PRECISION', 'fp32'), 'fp32_mfma': bool(_ENV.get('HGN_FP32_MFMA')), 'general_fwd': bool(_ENV.get('HGN_NO_EDGE_FWD')),
-             'fused_edge_bwd': not bool(_ENV.get('HGN_NO_FUSED_BWD')) and not bool(_ENV.get('HGN_FP32_MFMA'))}
+             'fused_edge_bwd': not bool(_ENV.get('HGN_NO_FUSED_BWD')) and not bool(_ENV.get('HGN_FP32_MFMA')),
+             'data_only': not bool(_ENV.get('HGN_NO_DATA_ONLY'))}
 _defaults_epoch = 0           # bumped when a default changes: packed weight images of every context are rebuilt on their next use
 _FUSED_SEG_MAX_ROWS = 65      # a segment of <= 65 consecutive rows touches at most two 64-row tiles
 _DEFER_NODE_WGRAD = not bool(_ENV.get('HGN_NO_DEFERRED_WGRAD'))
@@ -40,10 +42,11 @@ class Context:
     The current context is thread-local (`using`); an autograd Function records the context of its forward and hands it to its
     backward explicitly, because the engine runs backward passes on threads of its own."""
 
-    def __init__(self, precision=None, fused_edge_bwd=None, fp32_mfma=None, general_fwd=None):
+    def __init__(self, precision=None, fused_edge_bwd=None, fp32_mfma=None, general_fwd=None, data_only=None):
         if precision is not None and precision not in _PRODUCTS:
             raise ValueError("matmul precision must be one of " + ', '.join(repr(k) for k in _PRODUCTS))
         self.precision, self.fused_edge_bwd, self.fp32_mfma, self.general_fwd = precision, fused_edge_bwd, fp32_mfma, general_fwd
+        self.data_only = data_only        # frozen MLPs (is_frozen) skip their z saves and weight-gradient launches; False: today's launches
         self.wgrad_stream = None          # weight-gradient launches go to this side stream (parallel.DataParallelTrainer)
         self.wq = {}                      # (M, device) -> [tasks, tensors kept alive, set of queued dW / db target addresses]
         self.wq_graph_task = -1           # id of the autograd engine run whose final callback will flush the queue (-1: none armed)
@@ -80,6 +83,9 @@ class Context:
     def fused(self) -> bool:
         return self.fused_edge_bwd if self.fused_edge_bwd is not None else _DEFAULTS['fused_edge_bwd']
 
+    def skips_frozen(self) -> bool:
+        return self.data_only if self.data_only is not None else _DEFAULTS['data_only']
+
     def stamp(self, args) -> None:
         """Fill the per-call options of an MlpFwd / MlpBwd / WTask."""
         args.products, args.flags = self.products(), self.flags()
@@ -106,7 +112,8 @@ class Context:
         return ws
 
     def __getstate__(self):               # a pickled model starts with a fresh queue / cache (settings travel)
-        return {'precision': self.precision, 'fused_edge_bwd': self.fused_edge_bwd, 'fp32_mfma': self.fp32_mfma, 'general_fwd': self.general_fwd}
+        return {'precision': self.precision, 'fused_edge_bwd': self.fused_edge_bwd, 'fp32_mfma': self.fp32_mfma, 'general_fwd': self.general_fwd,
+                'data_only': self.data_only}
 
     def __setstate__(self, st):
         self.__init__(**st)
@@ -442,14 +449,31 @@ def _fill_common_fwd(a: _lib.MlpFwd, w: MLPWeights, out, res, saves):
     a.out = out.data_ptr(); a.ld_out = _ld(out)
     if saves is not None:
         z1, z2, xhat, rstd, bits = saves
-        a.z1 = z1.data_ptr(); a.z2 = z2.data_ptr(); a.relu_bits = bits.data_ptr()
+        if z1 is not None:
+            a.z1 = z1.data_ptr(); a.z2 = z2.data_ptr()
+        a.relu_bits = bits.data_ptr()
         if xhat is not None:
             a.xhat = xhat.data_ptr(); a.rstd = rstd.data_ptr()
 
 
-def _alloc_saves(M, has_ln, dev):
-    z1 = torch.empty(M, LAT, device=dev)
-    z2 = torch.empty(M, LAT, device=dev)
+bwd_stats = {'data_only': 0, 'full': 0}         # backward nodes (MLPFn / EdgeBlockFn) that ran without / with their weight-gradient work
+
+
+def _frozen_rule(grad_on, src_flags, w_flags) -> bool:
+    return bool(grad_on) and any(src_flags) and not any(w_flags)
+
+
+def is_frozen(srcs, wt) -> bool:
+    """An MLP is FROZEN in a call when grad mode is on, at least one of its sources requires grad and none of its weight tensors
+    does (six, or eight with LayerNorm): its backward then forms data gradients only -- the forward saves no z1 / z2 (only
+    weight-gradient kernels read them), the backward stores no dz3 / dz2 and launches no weight-gradient or LayerNorm-affine sum.
+    Only requires_grad=False counts: torch.autograd.grad(loss, inputs) on a trainable model takes the full path."""
+    return _frozen_rule(torch.is_grad_enabled(), [t is not None and t.requires_grad for t in srcs], [t.requires_grad for t in wt])
+
+
+def _alloc_saves(M, has_ln, dev, keep_z=True):
+    z1 = torch.empty(M, LAT, device=dev) if keep_z else None
+    z2 = torch.empty(M, LAT, device=dev) if keep_z else None
     xhat = torch.empty(M, LAT, device=dev) if has_ln else None
     rstd = torch.empty(M, device=dev) if has_ln else None
     bits = torch.empty(M, 8, dtype=torch.int32, device=dev)      # ReLU sign patterns: what the backward chain reads instead of z1 / z2
@@ -771,6 +795,21 @@ def join(h: torch.Tensor):
     return _JoinFn.apply(h)
 
 
+def _ungather(ctx, c: Context, srcs, idxs, dxs, M):
+    """The last step of MLPFn.backward: source gradients back to the rows of their sources (gathered sources), offered to / withdrawn
+    from the edge blocks' accumulation (share_grad).  -> dxs"""
+    for i in range(len(dxs)):
+        if dxs[i] is not None and idxs[i] is not None:
+            full = torch.zeros_like(srcs[i])
+            full.index_add_(0, idxs[i].long(), dxs[i])
+            dxs[i] = full
+        elif dxs[i] is not None and i == 0 and ctx.share and srcs[i].shape[1] == LAT and M > 0:
+            share_grad(c, srcs[i], dxs[i])
+        elif dxs[i] is not None:
+            unshare_grad(c, srcs[i])
+    return dxs
+
+
 class MLPFn(torch.autograd.Function):
     """out = [src[residual] +] [LN](MLP(cat(src_0[idx_0], src_1[idx_1], ...)))   without materialising the cat."""
 
@@ -822,7 +861,9 @@ class MLPFn(torch.autograd.Function):
             a.W3pk = pk.data_ptr() + (nb1 + 1) * _lib.PACK_BLOCK_BYTES
         if given is None and col != w.w1.shape[1]:
             raise _lib.HgnError(f'MLP input width {col} does not match weight in_features {w.w1.shape[1]}')
-        saves = _alloc_saves(M, has_ln, dev) if train else None
+        # (`train` was taken with grad mode as the caller had it; ctx.needs_input_grad: which tensors require grad)
+        frozen = c.skips_frozen() and _frozen_rule(train, ctx.needs_input_grad[1:1 + n_src], ctx.needs_input_grad[1 + n_src:])
+        saves = _alloc_saves(M, has_ln, dev, not frozen) if train else None
         res = srcs[residual] if residual >= 0 else None
         _fill_common_fwd(a, w, out, res, saves)
         if post is not None:
@@ -847,6 +888,7 @@ class MLPFn(torch.autograd.Function):
             ctx.gaps = sum(s.shape[1] for s in srcs) != w.w1.shape[1]      # W1 columns no source feeds: their gradient is zero
             ctx.share = share
             ctx.saves = saves
+            ctx.frozen = frozen
             ctx.targets = _grad_targets(wt)
             ctx.pk_t = packs_of(w, transposed=True, ctx=c) if pk is not None else None
             ctx.hgn = c
@@ -866,18 +908,24 @@ class MLPFn(torch.autograd.Function):
         d_out = _rowmajor(d_out)
         L = _lib.lib()
         out_w = w.w3.shape[0]
-        dz3 = torch.empty(M, LAT, device=dev)
-        dz2 = torch.empty(M, LAT, device=dev)
-        dz1 = torch.empty(M, LAT, device=dev)
+        frozen = ctx.frozen                # data gradients only: no dz arrays, no weight-gradient task, nothing queued
+        bwd_stats['data_only' if frozen else 'full'] += 1
         b = _lib.MlpBwd()
         c.stamp(b)
         b.M = M
         b.d_out = d_out.data_ptr(); b.ld_dout = _ld(d_out); b.out_w = out_w
         if has_ln:
             b.ln_g = w.ln_w.data_ptr(); b.xhat = xhat.data_ptr(); b.rstd = rstd.data_ptr()
-        b.z2 = z2.data_ptr(); b.z1 = z1.data_ptr(); b.relu_bits = bits.data_ptr()
+        b.relu_bits = bits.data_ptr()
         b.W3 = w.w3.data_ptr(); b.W2 = w.w2.data_ptr(); b.ldw1 = w.w1.shape[1]
-        b.dz3 = dz3.data_ptr(); b.dz2 = dz2.data_ptr(); b.dz1 = dz1.data_ptr()
+        if frozen:
+            b.flags |= _lib.F_DATA_ONLY
+        else:
+            dz3 = torch.empty(M, LAT, device=dev)
+            dz2 = torch.empty(M, LAT, device=dev)
+            dz1 = torch.empty(M, LAT, device=dev)
+            b.z2 = z2.data_ptr(); b.z1 = z1.data_ptr()
+            b.dz3 = dz3.data_ptr(); b.dz2 = dz2.data_ptr(); b.dz1 = dz1.data_ptr()
         dxs = [None] * n_src
         nd = 0
         for i in range(n_src):
@@ -896,6 +944,12 @@ class MLPFn(torch.autograd.Function):
             nb1 = (w.w1.shape[1] + LAT - 1) // LAT
             b.W2pk_t = pk_t.data_ptr() + nb1 * _lib.PACK_BLOCK_BYTES
             b.W3pk_t = pk_t.data_ptr() + (nb1 + 1) * _lib.PACK_BLOCK_BYTES
+        if frozen:
+            if has_ln:           # the split kernels write their LayerNorm partial slabs unconditionally: a workspace nobody sums
+                b.ln_ws = _ln_workspace(c, M, dev).data_ptr()
+            if M > 0:
+                _lib.check(L.hgn_mlp_bwd(C.byref(b), _lib.stream_ptr()), 'hgn_mlp_bwd')
+            return (None, *_ungather(ctx, c, srcs, idxs, dxs, M), *([None] * len(wt)))
         bufs, accs, grads_w = _grad_bufs(wt, ctx.targets)
         if has_ln:           # LayerNorm-affine gradients come out of the same pass
             b.d_gamma = bufs[6].data_ptr(); b.d_beta = bufs[7].data_ptr(); b.ln_accumulate = accs[6]
@@ -925,17 +979,7 @@ class MLPFn(torch.autograd.Function):
             dw1.zero_()
         # (gathered / narrow sources = encoders: few launches, operands of E rows: not worth keeping alive)
         _run_wgrad(c, tasks, M, dev, keep=[z1, z2, dz1, dz2, dz3, *srcs], defer=all(i is None for i in idxs) and pk_t is not None)
-        # ---- un-gather source gradients -----------------------------------------------------------------------
-        for i in range(n_src):
-            if dxs[i] is not None and idxs[i] is not None:
-                full = torch.zeros_like(srcs[i])
-                full.index_add_(0, idxs[i].long(), dxs[i])
-                dxs[i] = full
-            elif dxs[i] is not None and i == 0 and ctx.share and srcs[i].shape[1] == LAT and M > 0:
-                share_grad(c, srcs[i], dxs[i])
-            elif dxs[i] is not None:
-                unshare_grad(c, srcs[i])
-        return (None, *dxs, *grads_w)
+        return (None, *_ungather(ctx, c, srcs, idxs, dxs, M), *grads_w)
 
 
 def fused_mlp(srcs: Sequence[torch.Tensor], w: MLPWeights, idxs: Optional[Sequence[Optional[torch.Tensor]]] = None,
@@ -1037,7 +1081,8 @@ class EdgeBlockFn(torch.autograd.Function):
         # (the indices are global row numbers: the bases are those of row 0, which only exists when the part starts there)
         a.add[0].P = Ps - 4 * ldp * off_s; a.add[0].ld = ldp; a.add[0].idx = topo.snd.data_ptr()
         a.add[1].P = Pr - 4 * ldp * off_r; a.add[1].ld = ldp; a.add[1].idx = topo.rcv.data_ptr()
-        saves = _alloc_saves(E, True, dev) if train else None
+        frozen = c.skips_frozen() and _frozen_rule(train, ctx.needs_input_grad[5:8], ctx.needs_input_grad[8:])
+        saves = _alloc_saves(E, True, dev, not frozen) if train else None
         _fill_common_fwd(a, w, out, e, saves)
         agg, amax, amin, smean = None, None, None, None
         # `sum` aggregation inside the edge kernel itself (no second pass over e') when the segments are short enough for the
@@ -1079,6 +1124,7 @@ class EdgeBlockFn(torch.autograd.Function):
             ctx.set_materialize_grads(False)
             ctx.topo = topo
             ctx.saves = saves
+            ctx.frozen = frozen
             ctx.agg = (agg_ops, amax, amin)
             ctx.targets = _grad_targets(wt)
             ctx.pk_t = packs_of(w, transposed=True, ctx=c) if pk is not None else None
@@ -1109,6 +1155,8 @@ class EdgeBlockFn(torch.autograd.Function):
         if d_out is None and d_agg is None:
             return (None,) * (8 + len(wt))
         dev = (d_out if d_out is not None else d_agg).device
+        frozen = ctx.frozen           # data gradients only: hgn_mlp_bwd with F_DATA_ONLY (never the fused kernel), no weight-gradient task
+        bwd_stats['data_only' if frozen else 'full'] += 1
         dz3 = dz2 = None              # [E,128] each, only on the two-launch path (the fused kernel keeps them on chip)
         dz1 = torch.empty((E + 63) // 64 * 64, LAT, device=dev)[:E]      # whole 64-row tiles: hgn_edge_bwd_fused stores the padding rows too
         de = torch.empty(E, LAT, device=dev)
@@ -1142,7 +1190,9 @@ class EdgeBlockFn(torch.autograd.Function):
             b.agg_argmax = amax.data_ptr() - 4 * LAT * off_r if amax is not None else None
             b.agg_argmin = amin.data_ptr() - 4 * LAT * off_r if amin is not None else None
         b.ln_g = w.ln_w.data_ptr(); b.xhat = xhat.data_ptr(); b.rstd = rstd.data_ptr()
-        b.z2 = z2.data_ptr(); b.z1 = z1.data_ptr(); b.relu_bits = bits.data_ptr()
+        if not frozen:
+            b.z2 = z2.data_ptr(); b.z1 = z1.data_ptr()
+        b.relu_bits = bits.data_ptr()
         b.W3 = w.w3.data_ptr(); b.W2 = w.w2.data_ptr(); b.ldw1 = 3 * LAT
         b.dz1 = dz1.data_ptr()
         b.n_dx = 1
@@ -1153,11 +1203,16 @@ class EdgeBlockFn(torch.autograd.Function):
             d.Wpk_t = pk_t.data_ptr() + 2 * _lib.PACK_BLOCK_BYTES
             b.W2pk_t = pk_t.data_ptr() + 3 * _lib.PACK_BLOCK_BYTES
             b.W3pk_t = pk_t.data_ptr() + 4 * _lib.PACK_BLOCK_BYTES
-        bufs, accs, grads_w = _grad_bufs(wt, ctx.targets)
-        dw1, db1, dw2, db2, dw3, db3, dg, dbt = bufs
-        b.d_gamma = dg.data_ptr(); b.d_beta = dbt.data_ptr(); b.ln_accumulate = accs[6]
-        if not _ln_defer(c, b, E, dev, dg, dbt, accs[6] and accs[7]):
+        if frozen:           # the split kernels write their LayerNorm partial slabs unconditionally: a workspace nobody sums
+            grads_w, accs = [None] * len(wt), None
+            b.flags |= _lib.F_DATA_ONLY
             b.ln_ws = _ln_workspace(c, E, dev).data_ptr()
+        else:
+            bufs, accs, grads_w = _grad_bufs(wt, ctx.targets)
+            dw1, db1, dw2, db2, dw3, db3, dg, dbt = bufs
+            b.d_gamma = dg.data_ptr(); b.d_beta = dbt.data_ptr(); b.ln_accumulate = accs[6]
+            if not _ln_defer(c, b, E, dev, dg, dbt, accs[6] and accs[7]):
+                b.ln_ws = _ln_workspace(c, E, dev).data_ptr()
         # dP = [sum over edges sent by n of dz1 | sum over edges received by n of dz1]; the receiver half comes out of the
         # backward kernel itself when the segments are short (include/hgn_mp.h: seg_dz1)
         if same:
@@ -1167,7 +1222,7 @@ class EdgeBlockFn(torch.autograd.Function):
             dP = (torch.empty(Ns, LAT, device=dev), torch.empty(Nr, LAT, device=dev))
             dPs, dPr, ldd = dP[0].data_ptr(), dP[1].data_ptr(), LAT
         # One pass for data gradients AND weight gradients (include/hgn_mp.h: hgn_edge_bwd_fused): dz3 / dz2 never reach memory.
-        may_fuse = c.fused() and pk_t is not None and E > 0 and c.wgrad_stream is None and accs[2] == accs[4]
+        may_fuse = not frozen and c.fused() and pk_t is not None and E > 0 and c.wgrad_stream is None and accs[2] == accs[4]
         fused = may_fuse and bool(L.hgn_edge_bwd_fused_eligible(C.byref(b)))      # (dW3 / dW2 share one accumulate flag in hgn_wfuse_t)
         if may_fuse and not fused and d_agg is not None:
             # Several aggregates (pna) or arg-routed ones: the fused kernel gathers ONE `sum` row per edge.  The gradient that reaches e'
@@ -1222,6 +1277,9 @@ class EdgeBlockFn(torch.autograd.Function):
             # dW1's edge block: dz1 is in memory anyway (the sender / receiver sums read it), one streaming task
             _run_wgrad(c, [_wtask(0, e.data_ptr(), _ld(e), LAT, None, dz1.data_ptr(), LAT, LAT, dw1.data_ptr() + 4 * 2 * LAT, 3 * LAT,
                                db1.data_ptr(), accs[0])], E, dev, edge_level=True, keep=[e, dz1])
+        elif frozen:         # dz1 is stored (the sender / receiver sums below read it); dz3 / dz2 never leave the chip
+            if E > 0:
+                _lib.check(L.hgn_mlp_bwd(C.byref(b), st), 'hgn_mlp_bwd')
         else:
             dz3 = torch.empty(E, LAT, device=dev)
             dz2 = torch.empty(E, LAT, device=dev)
@@ -1248,13 +1306,14 @@ class EdgeBlockFn(torch.autograd.Function):
             if not fuse_seg:
                 _lib.check(L.hgn_segment_reduce_fwd(dz1.data_ptr(), LAT, LAT, None, topo.r.rowptr.data_ptr() + 4 * off_r, Nr, ops, 1,
                                                     dPr, ldd, None, None, st), 'segment_reduce(receivers)')
-        task_s = _wtask(0, h_s.data_ptr(), _ld(h_s), LAT, None, dPs, ldd, LAT, dw1.data_ptr(), 3 * LAT, None, accs[0])
-        task_r = _wtask(0, h_r.data_ptr(), _ld(h_r), LAT, None, dPr, ldd, LAT, dw1.data_ptr() + 4 * LAT, 3 * LAT, None, accs[0])
-        if same:
-            _run_wgrad(c, [task_s, task_r], Ns, dev, keep=[h_s, dP], defer=True)
-        else:
-            _run_wgrad(c, [task_s], Ns, dev, keep=[h_s, dP[0]], defer=True)
-            _run_wgrad(c, [task_r], Nr, dev, keep=[h_r, dP[1]], defer=True)
+        if not frozen:
+            task_s = _wtask(0, h_s.data_ptr(), _ld(h_s), LAT, None, dPs, ldd, LAT, dw1.data_ptr(), 3 * LAT, None, accs[0])
+            task_r = _wtask(0, h_r.data_ptr(), _ld(h_r), LAT, None, dPr, ldd, LAT, dw1.data_ptr() + 4 * LAT, 3 * LAT, None, accs[0])
+            if same:
+                _run_wgrad(c, [task_s, task_r], Ns, dev, keep=[h_s, dP], defer=True)
+            else:
+                _run_wgrad(c, [task_s], Ns, dev, keep=[h_s, dP[0]], defer=True)
+                _run_wgrad(c, [task_r], Nr, dev, keep=[h_r, dP[1]], defer=True)
         # inputs: topo, train, agg_ops, pre, parts, h_s, h_r, e, *weights
         dhs = [None, None]
         for slot, (need, n, b0, nb, gptr) in enumerate(((ctx.needs_input_grad[5], Ns, 0, 2 if same else 1, dPs),

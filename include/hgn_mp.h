@@ -42,6 +42,9 @@ extern "C" {
 #define HGN_F_GENERAL_FWD 2
 #define HGN_F_TILE64_FWD 4   /* A/B switch: 64-row forward tiles (three workgroups per CU) also for launches that would take 128-row tiles */
 #define HGN_F_DEFER_LN 8     /* hgn_mlp_bwd / hgn_edge_bwd_fused: leave the LayerNorm partial slabs in ln_ws; the caller sums them later with hgn_ln_reduce_batch */
+#define HGN_F_DATA_ONLY 16   /* hgn_mlp_bwd: the data gradients alone (the MLP's weights get no gradient): dz3 / dz2 must be null, d_gamma /
+                              * d_beta may be, no LayerNorm sums are taken (ln_ws is still required where the split kernels need it: they write
+                              * their partial slabs unconditionally).  hgn_edge_bwd_fused* and hgn_mlp_wgrad* refuse a call that carries it. */
 
 #define HGN_MAX_SRC 8
 #define HGN_MAX_ADD 2
@@ -158,6 +161,8 @@ int hgn_segment_std_bwd(const float* d_out, const float* out, const float* mean,
  *           cat + 3 Linear + LN + add) and LazyMLP (meshgraphnet.py:93-108) for encoder / decoder.
  * Weights are nn.Linear layout [out][in] addressed in place (pointer + leading dimension); nothing is
  * repacked.  Saved activations (z1, z2 post-ReLU, xhat, rstd) are written when non-null (training).
+ * z1 == z2 == NULL with relu_bits (and, with LayerNorm, xhat / rstd) present is the training forward for a backward WITHOUT weight
+ * gradients (hgn_mlp_bwd with HGN_F_DATA_ONLY): only weight-gradient kernels read z1 / z2, the data chain reads the sign words.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct {
   const float* x;      /* [rows, ld] source rows                                   */
@@ -258,6 +263,10 @@ int hgn_set_matmul_products(int n /* 3, 6, 1 or 2 */);
 int hgn_get_matmul_products(void);
 int hgn_mlp_fwd6_eligible(const hgn_mlp_fwd_t* args /*host*/);   /* 1 if hgn_mlp_fwd will take the split-bf16 kernel */
 int hgn_mlp_fwd_post_eligible(const hgn_mlp_fwd_t* args /*host*/);   /* 1 if hgn_mlp_fwd accepts these args WITH their post_* fields */
+/* Which kernel hgn_mlp_fwd takes for these arguments (shapes and pointers only, never data; host only): 0 a general kernel, 1 the
+ * training-edge-block kernel with its z1 / z2 saves, 2 the same kernel without them (z1 == z2 == NULL).  Row threshold (98 304),
+ * product mode (3 and 6 only) and HGN_F_GENERAL_FWD as the launch decides them; exactly one of z1 / z2 null: 0. */
+int hgn_mlp_fwd_edge_form(const hgn_mlp_fwd_t* args /*host*/);
 int hgn_linear_fwd6(const float* x, int64_t ldx, int64_t M, const void* const* packed_blocks /*host array*/, int n_blocks,
                     float* out, int64_t ld_out, int products /*0 = process default, or 3 / 6 / 1 / 2*/, void* stream);
 /* The same launch, which also sets zero_rows[i][0..128) = 0 for i < M (nullable; leading dimension ld_zero >= 128, a multiple of

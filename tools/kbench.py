@@ -12,6 +12,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=64)
 ap.add_argument('--iters', type=int, default=3)
 ap.add_argument('--what', default='edge,seg')
+ap.add_argument('--frozen', action='store_true', help='parameters without gradients: forward without z1 / z2, data-only backward')
 a = ap.parse_args()
 g = synthetic.batch([synthetic.grid_graph(seed=i % 4) for i in range(a.batch)])
 es = g.edge_sets[0]
@@ -21,6 +22,8 @@ dev = torch.device('cuda')
 topo = topology.EdgeTopology(es.senders, es.receivers, N, dev)
 torch.manual_seed(0)
 m = hgn_amd.MeshGraphNet(3, 128, 2, 'sum', 1, 'none', ['mesh_edges']).to(dev)
+if a.frozen:
+    m.requires_grad_(False)
 blk = m.processor.graphnet_blocks[0]
 w = modules.weights_of(blk.edge_models['mesh_edges'], 384)
 wn = modules.weights_of(blk.node_model_cross, 256)

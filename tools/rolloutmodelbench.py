@@ -8,7 +8,9 @@ and in lock step, M windows per union graph (`model.nstep_batch = M`), and wheth
 With `--unroll N` the tool does one thing instead: it times ONE `unrolled_training_step` of N steps including `backward()`
 (through_state=True, frozen statistics) on the 40x40 flag mesh (none/sum/L15), for `--unroll-windows` windows in lock step and for one
 window, against the same loss written with the ops the package had before that method: per step build_graph_batch -> network ->
-`update` -> torch.where.  The two forms alternate inside one process; the object holds the mean and the smallest time of each."""
+`update` -> torch.where.  The two forms alternate inside one process; the object holds the mean and the smallest time of each.
+With `--frozen` the parameters of learned_model do not require grad and frame 0 of world_pos / prev|world_pos does: the backward pass
+forms the gradients of the initial state only (data-only backward of frozen MLPs)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, 'hyper-graph-nets_amd')):
@@ -80,12 +82,21 @@ def unroll_times(a):
         windows = {k: torch.stack([torch.stack([f[k] for f in row]) for row in frames]).cuda()
                    for k in ('world_pos', 'prev|world_pos', 'target|world_pos', 'node_type')}
         windows['cells'], windows['mesh_pos'] = warm['cells'], warm['mesh_pos']
+        leaves = []
+        if a.frozen:            # the network's parameters get no gradient; the loss is differentiated with respect to the initial state
+            model.learned_model.requires_grad_(False)
+            for k in ('world_pos', 'prev|world_pos'):
+                leaf = windows[k][:, 0].clone().requires_grad_(True)
+                windows[k] = torch.cat([leaf.unsqueeze(1), windows[k][:, 1:]], dim=1)
+                leaves.append(leaf)
         forms = {'unrolled_training_step': lambda: model.unrolled_training_step(windows, a.unroll, True, False)[0],
                  'per_step_ops': lambda: loop_unroll(model, windows, a.unroll)}
         times, losses = {k: [] for k in forms}, {}
         for rep in range(2 + a.unroll_repeats):                # two warm rounds: lazy state, topology caches
             for name, fn in forms.items():
                 model.zero_grad(set_to_none=True)
+                for leaf in leaves:
+                    leaf.grad = None
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 loss = fn()
@@ -103,6 +114,7 @@ def unroll_times(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--unroll', type=int, default=0, help='time one unrolled_training_step of N steps with backward() instead')
+    ap.add_argument('--frozen', action='store_true', help='with --unroll: freeze learned_model, differentiate with respect to the initial state')
     ap.add_argument('--unroll-windows', type=int, default=8)
     ap.add_argument('--unroll-repeats', type=int, default=10)
     ap.add_argument('--steps', type=int, default=100)
