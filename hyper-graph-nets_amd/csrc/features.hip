@@ -250,6 +250,37 @@ __global__ void rollout_advance_bwd_kernel(const float* __restrict__ d_next, lon
   if (d_fb) d_fb[r * ld_df + c] = (is_free || !has_fallback) ? 0.f : g;
 }
 
+// Backward of the cluster mean of the connector (hierarchical_connector.py:39-45; rmp.py: `means_all = ...` in
+// HierarchicalConnector.run) with respect to the node rows.  Node-parallel, flat over [rows, D]: thread (n, c) walks row n's own
+// memberships q in [node_rowptr[n], node_rowptr[n+1]) in that order -- j = node_items[q] is a position of the member list, s =
+// item_seg[j] its cluster -- and adds d_mean[s, c] / (float)count(s), the expression of seg_bwd_generic_kernel's HGN_OP_MEAN
+// branch (segment.hip), so a partition of the rows gives that kernel's bits.  Every element is written exactly once, 0 for a row
+// in no cluster (obstacle rows, noise, rows a sampling left out): no atomics, no LDS, no pre-zeroed output, equal bits on every run.
+// Ids outside their ranges are skipped, never dereferenced.
+__global__ void member_mean_bwd_kernel(const float* __restrict__ d_mean, long ld_dm, int D, const int* __restrict__ seg_rowptr,
+                                       long S, const int* __restrict__ item_seg, const int* __restrict__ node_rowptr,
+                                       const int* __restrict__ node_items, long rows, long M, float* __restrict__ d_data,
+                                       long ld) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * D) return;
+  const long n = i / D;
+  const int c = (int)(i - n * D);
+  float g = 0.f;
+  if (M > 0) {
+    const int q0 = node_rowptr[n], q1 = node_rowptr[n + 1];
+    for (int q = q0; q < q1; ++q) {
+      if (q < 0 || q >= M) continue;
+      const long j = node_items[q];
+      if (j < 0 || j >= M) continue;
+      const long s = item_seg[j];
+      if (s < 0 || s >= S) continue;
+      const int cnt = seg_rowptr[s + 1] - seg_rowptr[s];
+      g += d_mean[s * ld_dm + c] / (float)(cnt > 0 ? cnt : 1);
+    }
+  }
+  d_data[n * ld + c] = g;
+}
+
 // ----------------------------------------------------------------------------------------------------------
 // world edges by radius: one wavefront per sender row, receivers in chunks of 64 (ballot keeps ascending order)
 // ----------------------------------------------------------------------------------------------------------
@@ -793,6 +824,25 @@ extern "C" int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, co
                      (unsigned)free_mask, has_fallback, (long)rows, d_net, (long)ld_dnet, d_cur, (long)ld_dcur, d_prev,
                      (long)ld_dprev, d_fallback, (long)ld_dfb);
   return hgn_check_launch("hgn_rollout_advance_bwd");
+}
+
+extern "C" int hgn_member_mean_bwd(const float* d_mean, int64_t ld_dmean, int D, const int32_t* seg_rowptr, int64_t S,
+                                  const int32_t* item_seg, const int32_t* node_rowptr, const int32_t* node_items, int64_t rows,
+                                  int64_t M, float* d_data, int64_t ld, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (D < 1 || ld < D || ld_dmean < D) return hgn_fail(HGN_E_INVALID, "hgn_member_mean_bwd: bad widths / strides (D >= 1, ld >= D, ld_dmean >= D)");
+  if (rows < 0 || rows > 0x7fffffff || M < 0 || M > 0x7fffffff || S < 0 || S > 0x7fffffff)
+    return hgn_fail(HGN_E_INVALID, "hgn_member_mean_bwd: bad sizes (0 <= rows, M, S < 2^31)");
+  if ((rows > 0 && !d_data) || (rows > 0 && M > 0 && (!d_mean || !seg_rowptr || !item_seg || !node_rowptr || !node_items)))
+    return hgn_fail(HGN_E_INVALID, "hgn_member_mean_bwd: null pointer");
+  if (M > 0 && S < 1) return hgn_fail(HGN_E_INVALID, "hgn_member_mean_bwd: members without a segment (M > 0 needs S >= 1)");
+  if (rows == 0) return HGN_OK;
+  const int64_t n = rows * D;
+  if ((n + 255) / 256 > 0x7fffffff) return hgn_fail(HGN_E_INVALID, "hgn_member_mean_bwd: rows * D does not fit one launch");
+  ProfScope ps(13, (double)rows, stream);
+  hipLaunchKernelGGL(member_mean_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_mean, (long)ld_dmean, D,
+                     seg_rowptr, (long)S, item_seg, node_rowptr, node_items, (long)rows, (long)M, d_data, (long)ld);
+  return hgn_check_launch("hgn_member_mean_bwd");
 }
 
 extern "C" int hgn_radius_edges_workspace_bytes(int64_t N, size_t* bytes) {

@@ -286,6 +286,46 @@ class _ClusterTopology:
         self.inter_r = (one.inter_r.repeat(B) + shift).contiguous()
         return self
 
+    _node_side = None
+
+    def node_side(self):
+        """What the backward of the cluster mean walks (hgn_member_mean_bwd), built at the first gradient and kept: the member
+        list as a CSR over the B*N node rows -- row n's memberships, as positions of the member list in ascending order -- and the
+        cluster of every position as int32.  -> (rowptr [rows + 1], items [M], item_seg [M], rows)."""
+        if self._node_side is None:
+            rows = self.B * self.N
+            csr = topology.segment_csr(self.members, rows, self.members.device)
+            self._node_side = (csr.rowptr, csr.perm.contiguous(), self.label.to(torch.int32).contiguous(), rows)
+        return self._node_side
+
+
+class _MemberMeanFn(torch.autograd.Function):
+    """The cluster means of HierarchicalConnector.run as an autograd node.  Forward: the launch ops.aggregate(('mean',)) makes
+    without gradients (hgn_segment_reduce_fwd over the member rows), on detached rows.  Backward: hgn_member_mean_bwd, node-parallel
+    over the rows -- ops.AggregateFn.backward runs over as many items as its input has rows, and the member list is shorter than
+    that wherever rows belong to no cluster (obstacle rows, HDBSCAN noise, intra-cluster sampling)."""
+
+    @staticmethod
+    def forward(ctx, both, t):
+        ctx.topo, ctx.like = t, (tuple(both.shape), both.device, both.dtype)
+        return ops.aggregate([both.detach()], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_mean):
+        from . import _lib
+        t, (shape, dev, dtype) = ctx.topo, ctx.like
+        rowptr, items, item_seg, rows = t.node_side()
+        if shape[0] != rows:
+            raise _lib.HgnError(f'member mean backward: {shape[0]} rows, the cluster topology spans {rows}')
+        g = features._f32_rows(d_mean.to(dev))
+        D = shape[1]
+        d_data = torch.empty(rows, D, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().hgn_member_mean_bwd(
+            features._ptr(g), features._ld(g), D, t.csr.rowptr.data_ptr(), t.csr.rowptr.shape[0] - 1, features._ptr(item_seg),
+            rowptr.data_ptr(), features._ptr(items), rows, t.M, d_data.data_ptr(), D, _lib.stream_ptr()), 'hgn_member_mean_bwd')
+        return d_data.to(dtype), None
+
 
 class AbstractConnector:
     def __init__(self, fully_connect, noise_scale, hyper_node_features):
@@ -337,7 +377,10 @@ class HierarchicalConnector(AbstractConnector):
         C = cf.shape[1]
         # cluster means of [clustering features | node features]: one segment-mean pass over the member rows
         both = torch.cat((cf, nf), dim=1)
-        means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))     # :39-45
+        if features._needs_grad(both):                   # position gradients (AbstractSystemModel.position_gradients): same launch
+            means_all = _MemberMeanFn.apply(both, t)
+        else:
+            means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))     # :39-45
         means, nf_means = means_all[:, :C], means_all[:, C:]
         if noise is None and is_training and self._noise_scale is not None:                         # :48-51
             noise = torch.normal(torch.zeros_like(means), std=self._noise_scale)
@@ -422,10 +465,11 @@ class RemoteMessagePassing:
     def create_graph(self, graph: MultiGraphWithPos, is_training: bool) -> MultiGraph:
         graph = graph._replace(node_features=graph.node_features[0])          # :67
         if self._clusters is None:
-            if graph.obstacle_nodes is not None:
-                self.remove_obstacles(graph)
+            values = self._values(graph)                                      # labels are no function autograd could follow
+            if values.obstacle_nodes is not None:
+                self.remove_obstacles(values)
             else:
-                self._clusters = self._clustering_algorithm.run(graph)
+                self._clusters = self._clustering_algorithm.run(values)
             self._neighbors = self._clustering_algorithm.neigboring_clusters
         return self._node_connector.run(graph, self._clusters, self._neighbors, is_training)
 
@@ -435,13 +479,30 @@ class RemoteMessagePassing:
         over the union."""
         graph = graph._replace(node_features=graph.node_features[0])
         if self._clusters is None:
-            first = self._first_frame_graph(graph, n_graphs)
+            first = self._first_frame_graph(self._values(graph), n_graphs)
             if first.obstacle_nodes is not None:
                 self.remove_obstacles(first)
             else:
                 self._clusters = self._clustering_algorithm.run(first)
             self._neighbors = self._clustering_algorithm.neigboring_clusters
         return self._node_connector.run(graph, self._clusters, self._neighbors, is_training, n_graphs=n_graphs)
+
+    @staticmethod
+    def _values(graph: MultiGraphWithPos) -> MultiGraphWithPos:
+        """The graph as the clustering sees it: every tensor that requires grad replaced by its detached value (the clustering
+        algorithms, remove_obstacles and the sampling helpers hand tensors to numpy); the graph itself where none does."""
+        def val(t):
+            return t.detach() if torch.is_tensor(t) and t.requires_grad else t
+
+        def edges(es):
+            return es if es is None else EdgeSet(es.name, val(es.features), es.senders, es.receivers)
+        sets = [e for e in (*graph.edge_sets, graph.unnormalized_edges) if e is not None]
+        tensors = [graph.node_features, graph.target_feature, graph.mesh_features, graph.node_dynamic] + [e.features for e in sets]
+        if not any(torch.is_tensor(t) and t.requires_grad for t in tensors):
+            return graph
+        return graph._replace(node_features=val(graph.node_features), target_feature=val(graph.target_feature),
+                              mesh_features=val(graph.mesh_features), node_dynamic=val(graph.node_dynamic),
+                              unnormalized_edges=edges(graph.unnormalized_edges), edge_sets=[edges(e) for e in graph.edge_sets])
 
     @staticmethod
     def _first_frame_graph(graph: MultiGraphWithPos, n_graphs: int) -> MultiGraphWithPos:

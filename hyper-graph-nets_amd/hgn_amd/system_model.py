@@ -49,7 +49,7 @@ class LockStep(NamedTuple):
     free_types: Tuple[int, ...]     # node types that are integrated (and enter the loss)
     per_step: Tuple[str, ...]       # the per-step series get_target reads
     fallback: Optional[str]         # the per-step series a row that is not free is put on; None: it keeps its own state
-    differentiable: bool            # whether build_graph_batch is differentiable with respect to the state
+    differentiable: bool            # whether build_graph_batch is differentiable with respect to the state without `position_gradients`
     expand_steps: Optional[int]     # the num_steps a rollout hands to expand_graph_batch; None: the call's own
     record_before: bool             # a rollout records the state before the step (else the new one)
     inv_from: Optional[int]         # `inv_out` holds the inverse-normalised output columns from here on; None: not recorded
@@ -191,14 +191,19 @@ class AbstractSystemModel(nn.Module):
     def expand_graph(self, graph: MultiGraphWithPos, step: int, num_steps: int, is_training: bool) -> MultiGraph:
         """The optional stages between build_graph and the network, in the reference's order (flag.py:130-141,
         cylinder.py:108-119, plate.py:202-216): graph balancer first (appends the `balance` edge set, renormalises the mesh
-        edges), then remote message passing (hyper nodes + remote edge sets).  Neither stage is differentiable with respect to the
-        positions (clusters, curvature and the hyper-node statistics are functions of them): a graph that carries position gradients
-        is refused instead of losing them."""
-        if (self._balancer or self._rmp) and _carries_grad(
+        edges), then remote message passing (hyper nodes + remote edge sets).  Clusters, curvature and which member decides a hyper
+        node's spread are functions of the positions, so by default a graph that carries position gradients is refused instead of
+        losing them.  With
+        `position_gradients = True` the connector lets it in: the clustering reads detached values, the cluster means, spreads,
+        hyper-node features and remote edge features are differentiated (the means by hgn_member_mean_bwd, the rest by the backward
+        kernels of the frame -> graph step) and the labels, the spread winners and the noise sample are constants.  The graph balancer
+        refuses in either case."""
+        if (self._balancer or (self._rmp and not self.position_gradients)) and _carries_grad(
                 graph.target_feature, graph.mesh_features, *graph.node_features, *(e.features for e in graph.edge_sets)):
             raise _lib.HgnError('expand_graph: the graph balancer and remote message passing (connector) stages are not differentiable '
                                 'with respect to positions; build the graph from tensors that do not require grad, or under '
-                                'torch.no_grad(), or configure the model without these stages')
+                                'torch.no_grad(), or configure the model without these stages.  A connector alone takes such a graph '
+                                'with `model.position_gradients = True` (labels and spread winners are then constants)')
         if self._balancer:
             if self._refresh_due(step, num_steps, self._balance_frequency):
                 self._graph_balancer.reset_balancer()
@@ -220,16 +225,18 @@ class AbstractSystemModel(nn.Module):
         Semantic difference to B expand_graph calls: each normaliser accumulates ONCE, with the statistics of the whole batch, and
         `hyper_noise` is drawn once per call for all B*K hyper nodes.
         Out of scope: a configured graph balancer (HgnError) and meshes that differ within one batch.  Like expand_graph, a
-        connector refuses a graph that carries position gradients."""
+        connector refuses a graph that carries position gradients unless `position_gradients` is set."""
         if self._balancer:
             raise _lib.HgnError('expand_graph_batch: the graph balancer stage has no batched form; expand the frames one by one with '
                                 'expand_graph and batch them with batching.batch_graphs, or configure the model without a balancer')
         if not self._rmp:
             return MultiGraph(node_features=graph.node_features, edge_sets=graph.edge_sets)
-        if _carries_grad(graph.target_feature, graph.mesh_features, *graph.node_features, *(e.features for e in graph.edge_sets)):
+        if not self.position_gradients and _carries_grad(
+                graph.target_feature, graph.mesh_features, *graph.node_features, *(e.features for e in graph.edge_sets)):
             raise _lib.HgnError('expand_graph_batch: the remote message passing (connector) stage is not differentiable with respect to '
                                 'positions; build the graph from tensors that do not require grad, or under torch.no_grad(), or '
-                                'configure the model without this stage')
+                                'configure the model without this stage.  `model.position_gradients = True` lets the graph in (labels and '
+                                'spread winners are then constants)')
         if self._refresh_due(step, num_steps, self._rmp_frequency):
             self._remote_graph.reset_clusters()
         return self._remote_graph.create_graph_batch(graph, int(n_graphs), is_training)
@@ -288,6 +295,11 @@ class AbstractSystemModel(nn.Module):
 
     # ---- lock-step evaluation: W windows of one mesh advance as one batch of W frames -------------------------------
     nstep_batch = None      # None: n_step_computation rolls the windows out one by one (the reference's loop); M > 0: M at a time
+    # False: PlateModel's build_graph[_batch], a connector in expand_graph[_batch] and unrolled_training_step(through_state=True) for
+    # either refuse tensors that require grad.  True (opt-in): they carry the gradient of everything that is smooth in the positions
+    # -- means, differences, norms, normalisation -- and treat as constants what is piecewise constant in them: the cluster labels,
+    # which pairs are world edges, which member wins a spread maximum (and the noise sample and the normaliser statistics).
+    position_gradients = False
 
     @staticmethod
     def _window_start(windows: Dict[str, Tensor], name: str) -> Tensor:
@@ -388,7 +400,8 @@ class AbstractSystemModel(nn.Module):
         and the state terms of get_target of all later steps.  ``through_state=False`` (push-forward): the state is detached before
         the next step, so every step's loss differentiates the parameters at that step only; this needs no differentiable graph
         construction and therefore also works for PlateModel and for models with a connector, which refuse ``through_state=True``
-        with ``n_steps`` > 1.  A configured graph balancer raises what expand_graph_batch raises.
+        with ``n_steps`` > 1 unless `position_gradients` is set (the gradient then holds the cluster labels, the world-edge
+        membership and the spread winners of every step constant).  A configured graph balancer raises what expand_graph_batch raises.
         -> (loss = the mean of the per-step losses, the per-step losses detached [n_steps]).  ``n_steps`` = 1 is `training_step` on
         the batched graph, bit for bit.
         Out of scope: HIP-graph capture of the unrolled step; the data-parallel trainer (parallel.Trainer.step keeps its single-step
@@ -397,10 +410,10 @@ class AbstractSystemModel(nn.Module):
         n_steps = int(n_steps)
         if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (ls.state,) + ls.per_step):
             raise ValueError(f'unrolled_training_step: n_steps = {n_steps} needs windows of at least that many frames (and n_steps >= 1)')
-        if through_state and n_steps > 1 and (self._rmp or not ls.differentiable):
+        if through_state and n_steps > 1 and not self.position_gradients and (self._rmp or not ls.differentiable):
             raise _lib.HgnError('unrolled_training_step: through_state=True differentiates build_graph_batch and expand_graph_batch with '
                                 'respect to the state, which PlateModel and models with a connector cannot do; pass through_state=False '
-                                '(push-forward: the state is detached between the steps)')
+                                '(push-forward: the state is detached between the steps), or set `model.position_gradients = True`')
         cells, mesh_pos = self._shared_mesh(windows)
         node_type = windows['node_type'][:, 0].to(device).to(torch.int64)
         W, N = node_type.shape[0], node_type.shape[1]
@@ -657,7 +670,9 @@ class PlateModel(AbstractSystemModel):
         return connector if (self._rmp or connector == 'repeated') else 'none'        # plate.py:37-39
 
     def build_graph(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
-        """plate.py:69-200.  Not differentiable with respect to positions: the world edges are a radius query of them."""
+        """plate.py:69-200.  The world edges are a radius query of the positions: tensors that require grad are refused, unless
+        `position_gradients` is set -- then the query reads detached values, which pairs are world edges is a constant, and the world
+        and mesh edge features and the node features carry the gradient."""
         return self._build(inputs, is_training, batched=False)
 
     def build_graph_batch(self, inputs: Dict, is_training: bool) -> MultiGraphWithPos:
@@ -667,16 +682,17 @@ class PlateModel(AbstractSystemModel):
         batching.batch_graphs does); the fields are those build_graph fills, `obstacle_nodes` is [B*N].  The `world_edges` of all
         frames come from ONE radius query over the union (features.radius_edges_batch with the cached neighbour CSR of the one
         mesh): one host synchronisation for the batch instead of one per frame, and no pair crosses a frame.  Like build_graph,
-        not differentiable with respect to positions.
+        it refuses positions that require grad unless `position_gradients` is set.
         Semantic difference to B separate build_graph calls: each normaliser accumulates ONCE, with the statistics of the whole
         batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
         return self._build(inputs, is_training, batched=True)
 
     def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
-        if _carries_grad(inputs['world_pos'], inputs['mesh_pos'], inputs['target|world_pos']):
+        if not self.position_gradients and _carries_grad(inputs['world_pos'], inputs['mesh_pos'], inputs['target|world_pos']):
             raise _lib.HgnError(f"PlateModel.{'build_graph_batch' if batched else 'build_graph'} is not differentiable with respect to "
                                 'positions (its world edges are a radius query of world_pos); pass tensors that do not require grad, '
-                                'or call it under torch.no_grad()')
+                                'or call it under torch.no_grad(), or set `model.position_gradients = True` (which pairs are world '
+                                'edges is then a constant)')
         rows, B, N = self._frame_rows(inputs, ('world_pos', 'target|world_pos', 'node_type'), batched)
         world_pos, mesh_pos, node_type = rows['world_pos'], rows['mesh_pos'], rows['node_type']
         (senders, receivers), mesh = self._frame_edges(inputs['cells'], B, N, deform=True)
@@ -685,9 +701,9 @@ class PlateModel(AbstractSystemModel):
         nbr_rowptr = self._mesh_neighbours(*mesh, N, world_pos.device)
         query = (self._RADIUS, NodeType.OBSTACLE.value, NodeType.NORMAL.value, nbr_rowptr, self._nbr)
         if batched:
-            world_senders, world_receivers, _ = features.radius_edges_batch(world_pos, node_type, B, *query)
+            world_senders, world_receivers, _ = features.radius_edges_batch(_value(world_pos), node_type, B, *query)
         else:
-            world_senders, world_receivers = features.radius_edges(world_pos, node_type, *query)
+            world_senders, world_receivers = features.radius_edges(_value(world_pos), node_type, *query)
         world_edge_features, _ = features.rel_edge_features(world_pos, None, world_senders, world_receivers)
         world_edges = EdgeSet(name='world_edges', features=self._world_edge_normalizer(world_edge_features, is_training),
                               receivers=world_receivers, senders=world_senders)
@@ -701,7 +717,7 @@ class PlateModel(AbstractSystemModel):
         return MultiGraphWithPos(
             node_features=[self._node_normalizer(node_features, is_training)], edge_sets=[mesh_edges, world_edges],
             mesh_features=mesh_pos, target_feature=world_pos, model_type=self._model_type,
-            unnormalized_edges=EdgeSet(name='mesh_edges', features=mesh_edge_features, receivers=receivers,
+            unnormalized_edges=EdgeSet(name='mesh_edges', features=_value(mesh_edge_features), receivers=receivers,
                                        senders=senders),
             node_dynamic=None, obstacle_nodes=obstacle_nodes)
 

@@ -18,6 +18,7 @@
  *   model/flag.py:169-180,243, cylinder.py:155-165, plate.py:246-257,328
  *                                    one rollout step's state update            -> hgn_rollout_advance
  *                                    and its derivative (unrolled training)     -> hgn_rollout_advance_bwd
+ *   rmp/hierarchical_connector.py:39-45  derivative of the cluster means         -> hgn_member_mean_bwd
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
  *                                                                              hgn_normalizer_update, hgn_normalize
  */
@@ -228,6 +229,27 @@ int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, const float* 
                             float cp, const int64_t* node_type, int64_t ldt, uint32_t free_mask, int has_fallback,
                             int64_t rows, float* d_net, int64_t ld_dnet, float* d_cur, int64_t ld_dcur, float* d_prev,
                             int64_t ld_dprev, float* d_fallback, int64_t ld_dfb, void* stream);
+
+/* ---- backward of the connector's cluster mean (hierarchical_connector.py:39-45; rmp.py HierarchicalConnector.run, the line
+ * `means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))`) ----------------------------------
+ * mean[s] = (1 / count(s)) * sum of data[member] over the members of cluster s.  The member list has M entries and need not
+ * cover the rows: obstacle rows (remote_message_passing.py:82-137), HDBSCAN noise and rows that intra-cluster sampling left out
+ * belong to no cluster, and a row may be a member more than once.  hgn_segment_reduce_bwd cannot serve that: it runs over as
+ * many items as the output has rows and writes only the rows it meets.  This entry is node-parallel instead:
+ *   seg_rowptr [S+1]   CSR row pointer of the member list by cluster: count(s) = seg_rowptr[s+1] - seg_rowptr[s]
+ *   item_seg   [M]     cluster of member-list position j
+ *   node_rowptr [rows+1], node_items [M]   CSR of the member list by node row: the positions j at which row n is listed
+ *   d_data[n, c] = sum over q in [node_rowptr[n], node_rowptr[n+1]), in that order, of
+ *                  d_mean[item_seg[node_items[q]], c] / (float)count(.)          (g = 0.f; g += v / (float)cnt)
+ * ONE launch, flat over [rows, D], 256 threads per block; every element of d_data is written exactly once, 0 for a row in no
+ * cluster, so the buffer needs no initialisation; no atomics, no LDS, equal bits on every run.  The expression is that of
+ * hgn_segment_reduce_bwd's mean for D != 128: where the members are a partition of the rows the two agree bit for bit.
+ * d_mean [S, ld_dmean], d_data [rows, ld], D >= 1 columns, both row strides >= D.  Ids outside their range are skipped.
+ * HGN_E_INVALID: D < 1, ld < D, ld_dmean < D, rows / M / S outside [0, 2^31), M > 0 with S = 0, null d_data with rows > 0, any
+ * other null pointer with rows > 0 and M > 0.  rows = 0: no-op.  M = 0 with rows > 0: d_data is zero-filled. */
+int hgn_member_mean_bwd(const float* d_mean, int64_t ld_dmean, int D, const int32_t* seg_rowptr, int64_t S,
+                        const int32_t* item_seg, const int32_t* node_rowptr, const int32_t* node_items, int64_t rows,
+                        int64_t M, float* d_data, int64_t ld, void* stream);
 
 #ifdef __cplusplus
 }

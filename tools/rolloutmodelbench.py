@@ -10,7 +10,11 @@ With `--unroll N` the tool does one thing instead: it times ONE `unrolled_traini
 window, against the same loss written with the ops the package had before that method: per step build_graph_batch -> network ->
 `update` -> torch.where.  The two forms alternate inside one process; the object holds the mean and the smallest time of each.
 With `--frozen` the parameters of learned_model do not require grad and frame 0 of world_pos / prev|world_pos does: the backward pass
-forms the gradients of the initial state only (data-only backward of frozen MLPs)."""
+forms the gradients of the initial state only (data-only backward of frozen MLPs).
+With `--connector <name>` (`hyper`, `hetero`, `multi`; k-means, `--clusters` hyper nodes) the model of `--unroll` has that connector.  What
+is timed then is the method in its two modes, alternating in one process: `through_state=False` (push-forward) and, with
+`--position-gradients` (which sets `model.position_gradients = True`; a connector refuses `through_state=True` without it),
+`through_state=True`.  `--position-gradients` without a connector only sets the switch: the flag graph is differentiable either way."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, 'hyper-graph-nets_amd')):
@@ -71,12 +75,17 @@ def loop_unroll(model, windows, n_steps):
 def unroll_times(a):
     from hgn_amd import synthetic, system_model
     torch.manual_seed(0)
-    model = system_model.FlagModel(params('none', 0, 15, 'sum'))
+    remote = a.connector != 'none'
+    model = system_model.FlagModel(params(a.connector, a.clusters if remote else 0, 15, 'sum'))
+    model.position_gradients = bool(a.position_gradients)
     warm = {k: v.cuda() for k, v in synthetic.flag_frame(seed=100, nx=40, ny=40).items()}
     with torch.no_grad():
-        model.learned_model(model.build_graph(warm, True))
+        model.learned_model(model.expand_graph(model.build_graph(warm, True), 0, 10 ** 9, True))
         model.get_target(warm, True)
-    res = {'n_steps': a.unroll, 'nodes': 1600, 'message_passing_steps': 15, 'repeats': a.unroll_repeats}
+    res = {'n_steps': a.unroll, 'nodes': 1600, 'message_passing_steps': 15, 'repeats': a.unroll_repeats, 'connector': a.connector,
+           'position_gradients': bool(a.position_gradients)}
+    if remote:
+        res['clusters'] = a.clusters
     for W in dict.fromkeys((a.unroll_windows, 1)):
         frames = [[synthetic.flag_frame(seed=200 + 10 * w + t, nx=40, ny=40) for t in range(a.unroll)] for w in range(W)]
         windows = {k: torch.stack([torch.stack([f[k] for f in row]) for row in frames]).cuda()
@@ -89,8 +98,13 @@ def unroll_times(a):
                 leaf = windows[k][:, 0].clone().requires_grad_(True)
                 windows[k] = torch.cat([leaf.unsqueeze(1), windows[k][:, 1:]], dim=1)
                 leaves.append(leaf)
-        forms = {'unrolled_training_step': lambda: model.unrolled_training_step(windows, a.unroll, True, False)[0],
-                 'per_step_ops': lambda: loop_unroll(model, windows, a.unroll)}
+        if remote:              # the two modes of the method; through the state only where the switch lets the connector differentiate
+            forms = {'push_forward': lambda: model.unrolled_training_step(windows, a.unroll, False, False)[0]}
+            if a.position_gradients:
+                forms = {'through_state': lambda: model.unrolled_training_step(windows, a.unroll, True, False)[0], **forms}
+        else:
+            forms = {'unrolled_training_step': lambda: model.unrolled_training_step(windows, a.unroll, True, False)[0],
+                     'per_step_ops': lambda: loop_unroll(model, windows, a.unroll)}
         times, losses = {k: [] for k in forms}, {}
         for rep in range(2 + a.unroll_repeats):                # two warm rounds: lazy state, topology caches
             for name, fn in forms.items():
@@ -106,8 +120,10 @@ def unroll_times(a):
                     times[name].append((time.perf_counter() - t0) * 1e3)
                 losses[name] = float(loss.detach())
         res[f'W={W}'] = {f'{k}_ms': {'mean': sum(v) / len(v), 'min': min(v)} for k, v in times.items()}
-        res[f'W={W}']['losses_equal'] = losses['unrolled_training_step'] == losses['per_step_ops']
-        res[f'W={W}']['speedup_of_the_means'] = (res[f'W={W}']['per_step_ops_ms']['mean'] / res[f'W={W}']['unrolled_training_step_ms']['mean'])
+        res[f'W={W}']['losses'] = losses
+        if not remote:
+            res[f'W={W}']['losses_equal'] = losses['unrolled_training_step'] == losses['per_step_ops']
+            res[f'W={W}']['speedup_of_the_means'] = (res[f'W={W}']['per_step_ops_ms']['mean'] / res[f'W={W}']['unrolled_training_step_ms']['mean'])
     return res
 
 
@@ -115,6 +131,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--unroll', type=int, default=0, help='time one unrolled_training_step of N steps with backward() instead')
     ap.add_argument('--frozen', action='store_true', help='with --unroll: freeze learned_model, differentiate with respect to the initial state')
+    ap.add_argument('--connector', default='none', help='with --unroll: the connector of the model (hyper, hetero, multi); times the two modes')
+    ap.add_argument('--clusters', type=int, default=16, help='with --connector: the number of hyper nodes')
+    ap.add_argument('--position-gradients', action='store_true', help='with --unroll: set model.position_gradients = True')
     ap.add_argument('--unroll-windows', type=int, default=8)
     ap.add_argument('--unroll-repeats', type=int, default=10)
     ap.add_argument('--steps', type=int, default=100)
