@@ -250,6 +250,74 @@ __global__ void rollout_advance_bwd_kernel(const float* __restrict__ d_next, lon
   if (d_fb) d_fb[r * ld_df + c] = (is_free || !has_fallback) ? 0.f : g;
 }
 
+// Training noise (data/preprocessing.py:84-98), one thread per row.  The sample of a row is a pure function of (seed, draw, frame id,
+// node): Philox4x32-10 with counter (node, frame id, draw lo, draw hi) and key (seed lo, seed hi) gives four words, Box-Muller in
+// fp32 turns them into four normals, column c takes z_c.  Nothing depends on where the row sits in the batch.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&w)[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// u1 = (k_a + 0.5) 2^-23 lies in (0, 1) and is exact in fp32 (k < 2^23), u2 = k_b 2^-23 in [0, 1); the accurate library functions.
+__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& za, float& zb) {
+  const float u1 = ((float)(wa >> 9) + 0.5f) * 0x1p-23f;
+  const float u2 = (float)(wb >> 9) * 0x1p-23f;
+  const float rad = sqrtf(-2.f * logf(u1));
+  const float theta = 6.283185307179586f * u2;
+  za = rad * cosf(theta);
+  zb = rad * sinf(theta);
+}
+
+__global__ void training_noise_kernel(const float* __restrict__ x, long ldx, int d, const int64_t* __restrict__ node_type, long ldt,
+                                      unsigned free_mask, long rows, long rows_per_frame, const int64_t* __restrict__ frame_ids,
+                                      unsigned key0, unsigned key1, unsigned draw0, unsigned draw1, float std_,
+                                      const float* __restrict__ target, long ld_tgt, float target_scale, float* __restrict__ out_x,
+                                      long ld_ox, float* __restrict__ out_target, long ld_ot) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const int64_t t = node_type[r * ldt];
+  const bool is_free = t >= 0 && t < 32 && ((free_mask >> (unsigned)t) & 1u);
+  float z[4] = {0.f, 0.f, 0.f, 0.f};
+  if (is_free) {
+    const long f = r / rows_per_frame;
+    const unsigned node = (unsigned)(r - f * rows_per_frame);
+    const unsigned fid = frame_ids ? (unsigned)frame_ids[f] : (unsigned)f;
+    unsigned w[4];
+    philox4x32_10(node, fid, draw0, draw1, key0, key1, w);
+    box_muller(w[0], w[1], z[0], z[1]);
+    if (d > 2) box_muller(w[2], w[3], z[2], z[3]);
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c >= d) break;
+    const float xv = x[r * ldx + c];
+    if (!is_free) {                                                 // a copy, bit for bit (-0.0 and NaN payloads included)
+      out_x[r * ld_ox + c] = xv;
+      if (target) out_target[r * ld_ot + c] = target[r * ld_tgt + c];
+      continue;
+    }
+    // Plain products and sums: contraction is off in this file, so each is rounded on its own.  (__fmul_rn / __fadd_rn are inlined
+    // as ordinary operations that the compiler does fuse: the emitted code had v_fmac for x + std * z.)
+    const float nz = std_ * z[c];
+    out_x[r * ld_ox + c] = xv + nz;
+    if (target) {
+      const float scaled = target_scale * nz;
+      out_target[r * ld_ot + c] = target[r * ld_tgt + c] + scaled;
+    }
+  }
+}
+
 // Backward of the cluster mean of the connector (hierarchical_connector.py:39-45; rmp.py: `means_all = ...` in
 // HierarchicalConnector.run) with respect to the node rows.  Node-parallel, flat over [rows, D]: thread (n, c) walks row n's own
 // memberships q in [node_rowptr[n], node_rowptr[n+1]) in that order -- j = node_items[q] is a position of the member list, s =
@@ -824,6 +892,29 @@ extern "C" int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, co
                      (unsigned)free_mask, has_fallback, (long)rows, d_net, (long)ld_dnet, d_cur, (long)ld_dcur, d_prev,
                      (long)ld_dprev, d_fallback, (long)ld_dfb);
   return hgn_check_launch("hgn_rollout_advance_bwd");
+}
+
+extern "C" int hgn_training_noise(const float* x, int64_t ldx, int d, const int64_t* node_type, int64_t ldt, uint32_t free_mask,
+                                  int64_t rows, int64_t rows_per_frame, const int64_t* frame_ids, uint64_t seed, uint64_t draw,
+                                  float std_, const float* target, int64_t ld_tgt, float target_scale, float* out_x, int64_t ld_ox,
+                                  float* out_target, int64_t ld_ot, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (d < 1 || d > 4 || rows < 0 || rows > 0x7fffffff || rows_per_frame < 1 || rows % rows_per_frame != 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise: bad sizes (1 <= d <= 4, 0 <= rows < 2^31, rows_per_frame >= 1 and divides rows)");
+  if ((target == nullptr) != (out_target == nullptr))
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise: target and out_target must both be given or both be null");
+  if (ldx < d || ld_ox < d || ldt < 1 || (target && (ld_tgt < d || ld_ot < d)))
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (!(std_ >= 0.f) || std_ > 3.4028234e38f)
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise: the standard deviation must be finite and not negative");
+  if (rows == 0) return HGN_OK;
+  if (!x || !node_type || !out_x) return hgn_fail(HGN_E_INVALID, "hgn_training_noise: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  hipLaunchKernelGGL(training_noise_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, x, (long)ldx, d, node_type,
+                     (long)ldt, (unsigned)free_mask, (long)rows, (long)rows_per_frame, frame_ids, (unsigned)(seed & 0xffffffffu),
+                     (unsigned)(seed >> 32), (unsigned)(draw & 0xffffffffu), (unsigned)(draw >> 32), std_, target, (long)ld_tgt,
+                     target_scale, out_x, (long)ld_ox, out_target, (long)ld_ot);
+  return hgn_check_launch("hgn_training_noise");
 }
 
 extern "C" int hgn_member_mean_bwd(const float* d_mean, int64_t ld_dmean, int D, const int32_t* seg_rowptr, int64_t S,

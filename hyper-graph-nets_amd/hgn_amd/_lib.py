@@ -203,6 +203,9 @@ _SIGS = {
                                           C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_uint32,
                                           C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_int64, C.c_void_p]),
+    'hgn_training_noise': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_member_mean_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_rel_edge_features_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,

@@ -467,6 +467,83 @@ def advance_state(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int, 
     return _advance_into_fresh(net_out, normalizer, cur, d, ca, prev, cp, node_type, free_types, fallback, inv_from)
 
 
+def _noise_into_fresh(x, node_type, free_types, std, seed, draw, target, target_scale, rows_per_frame, frame_ids):
+    dev = x.device
+    shape, x = x.shape, _f32_rows(x)
+    rows, d = x.shape
+    if not 1 <= d <= 4:
+        raise ValueError(f'add_noise: x must have 1..4 columns, got {d}')
+    if target is not None:
+        target = _f32_rows(target.to(dev))
+        if target.shape != x.shape:
+            raise ValueError('add_noise: x / target shape mismatch')
+    nt, ldt = _type_column(node_type, dev, rows)
+    if nt.shape[0] != rows:
+        raise ValueError(f'add_noise: {nt.shape[0]} node types for {rows} rows')
+    free_mask = 0
+    for t in free_types:
+        if not 0 <= int(t) < 32:
+            raise ValueError('add_noise: free node types must lie in [0, 32)')
+        free_mask |= 1 << int(t)
+    per_frame = max(rows, 1) if rows_per_frame is None else int(rows_per_frame)
+    if per_frame < 1 or rows % per_frame:
+        raise ValueError(f'add_noise: {rows} rows do not split into frames of {rows_per_frame} rows')
+    if frame_ids is not None:
+        # ids travel as int64 and are read modulo 2^32; a Python int up to 2^64 - 1 keeps its low 64 bits
+        if not torch.is_tensor(frame_ids):
+            frame_ids = torch.tensor([((int(i) + (1 << 63)) % (1 << 64)) - (1 << 63) for i in frame_ids], dtype=torch.int64)
+        frame_ids = _ids(frame_ids.reshape(-1), dev)
+        if frame_ids.shape[0] != rows // per_frame:
+            raise ValueError(f'add_noise: {frame_ids.shape[0]} frame ids for {rows // per_frame} frames')
+    seed, draw = int(seed), int(draw)
+    if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 64):
+        raise ValueError('add_noise: seed and draw must lie in [0, 2^64)')
+    out_x = torch.empty(rows, d, dtype=torch.float32, device=dev)
+    out_t = torch.empty(rows, d, dtype=torch.float32, device=dev) if target is not None else None
+    _lib.check(_lib.lib().hgn_training_noise(
+        x.data_ptr(), _ld(x), d, nt.data_ptr(), ldt, free_mask, rows, per_frame, _ptr(frame_ids), seed, draw, float(std),
+        _ptr(target), _ld(target), float(target_scale), out_x.data_ptr(), _ld(out_x), _ptr(out_t), _ld(out_t), _lib.stream_ptr()),
+        'hgn_training_noise')
+    return out_x.reshape(shape), (out_t.reshape(shape) if out_t is not None else None)
+
+
+class _AddNoiseFn(torch.autograd.Function):
+    """The noise is additive and a masked row is a copy: both outputs have the identity as derivative.  The backward launches nothing."""
+
+    @staticmethod
+    def forward(ctx, x, target, args):
+        ctx.set_materialize_grads(False)
+        ctx.refs = (x, target)
+        return _noise_into_fresh(x.detach(), *args[:5], target.detach() if target is not None else None, *args[5:])
+
+    @staticmethod
+    def backward(ctx, d_x, d_target):
+        x, target = ctx.refs
+        return (_like(d_x, x) if ctx.needs_input_grad[0] else None,
+                _like(d_target, target) if target is not None and ctx.needs_input_grad[1] else None, None)
+
+
+def add_noise(x: torch.Tensor, node_type: torch.Tensor, free_types, std: float, seed: int, draw: int, target=None,
+              target_scale: float = 0.0, rows_per_frame=None, frame_ids=None):
+    """Seeded training noise for a batch of frames in one launch (hgn_training_noise; src/data/preprocessing.py:84-98,
+    Preprocessing._add_noise, which runs once per frame): on the rows whose node type is listed in ``free_types``,
+    ``noisy_x = x + n`` and ``noisy_target = target + target_scale * n`` with ``n = std * z``, z standard normal; every other row is
+    copied.  ``x`` [rows, d] (d = 1..4) holds rows / rows_per_frame frames of ``rows_per_frame`` rows each (None: one frame).
+    The generator is counter-based (Philox4x32-10, Box-Muller): the sample of a row is a function of ``seed``, ``draw`` (both in
+    [0, 2^64); e.g. the training step), the frame's id (``frame_ids``: a sequence or an int64 tensor of one id per frame, read modulo
+    2^32; None: 0, 1, ..) and the row's place in its frame -- not of the frame's place in the batch or of the rank that holds it.
+    -> (noisy_x, noisy_target or None): fresh tensors in the shape of ``x``; nothing is written into the inputs, which may be views
+    of a trajectory.  When ``x`` or ``target`` requires grad the call is an autograd node whose backward hands the two incoming
+    gradients back unchanged and launches nothing.
+    Out of scope: the connector's `hyper_noise` keeps torch.normal; the reference's own src/data/preprocessing.py path through the
+    shim is unchanged; noise inside captured graphs."""
+    _lib.require_gpu(x)
+    args = (node_type, tuple(free_types), float(std), seed, draw, float(target_scale), rows_per_frame, frame_ids)
+    if _needs_grad(x, target):
+        return _AddNoiseFn.apply(x, target, args)
+    return _noise_into_fresh(x, *args[:5], target, *args[5:])
+
+
 def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, sender_type: int, receiver_type: int,
                  nbr_rowptr=None, nbr=None):
     """plate.py:84-110: directed pairs closer than ``radius`` with the given endpoint types that are not mesh

@@ -383,9 +383,43 @@ class AbstractSystemModel(nn.Module):
             views[name] = series.as_strided((count, horizon) + tuple(series.shape[1:]), (series.stride(0),) + tuple(series.stride()))
         return views
 
+    # ---- seeded training noise: one launch for a batch of frames --------------------------------------------------------
+    noise_seed = None       # the seed `add_noise` uses when the call gives none; a plain value (it travels in pickles, old ones read None)
+
+    def add_noise(self, frames: Dict[str, Tensor], draw: int, frame_ids=None, seed=None) -> Dict[str, Tensor]:
+        """The reference's training noise (src/data/preprocessing.py:84-98, once per frame) for one frame ([N, .] series) or for
+        stacked frames ([B, N, .], what build_graph_batch takes) in ONE features.add_noise launch: normal(0, `noise`) on the NORMAL
+        rows of ``frames[field]``, and (1 - `gamma`) times the same sample on ``frames['target|' + field]``; `field`, `noise` and
+        `gamma` are the keys of the YAML's `model` section (`self._params`).  Only NodeType.NORMAL is perturbed, as in the reference
+        -- not `_LOCKSTEP.free_types`: the cylinder's loss mask also holds OUTFLOW, its noise does not.
+        The sample of a row depends on (``seed``, ``draw``, the frame's id, the node) alone: ``seed`` defaults to `self.noise_seed`
+        (ValueError if both are None), ``draw`` counts the draws (the training step, say) and frame b has id ``frame_ids[b]``,
+        default b.  A rank of a data-parallel run that passes the global ids of its frames gets the samples a single process gets.
+        -> a shallow copy of ``frames`` with `field` and `target|field` replaced by fresh tensors in the input's shape; every other
+        entry is the same object (the flag's `prev|world_pos` is untouched, as in the reference) and the inputs are not written.  A
+        scale of 0, or a `model` section without `noise`, returns the copy without a launch.
+        Out of scope: the connector's `hyper_noise` keeps torch.normal; the reference's own src/data/preprocessing.py path through
+        the shim is unchanged; noise inside captured graphs; parallel.DataParallelTrainer is untouched (a rank calls this with its
+        own frame ids before it builds its shard)."""
+        out = dict(frames)
+        scale = self._params.get('noise')
+        if not scale:
+            return out
+        seed = self.noise_seed if seed is None else seed
+        if seed is None:
+            raise ValueError('add_noise: no seed (pass `seed`, or set `model.noise_seed`)')
+        field = self._params.get('field')
+        x, target = frames[field].to(device), frames['target|' + field].to(device)
+        rows_per_frame = x.shape[-2]
+        noisy, noisy_target = features.add_noise(
+            x.reshape(-1, x.shape[-1]), frames['node_type'].to(device).reshape(-1, 1), (NodeType.NORMAL.value,), float(scale), seed,
+            draw, target.reshape(-1, target.shape[-1]), 1.0 - float(self._params.get('gamma')), rows_per_frame, frame_ids)
+        out[field], out['target|' + field] = noisy.reshape(x.shape), noisy_target.reshape(target.shape)
+        return out
+
     # ---- training on unrolled rollouts: the W windows advance in lock step, with autograd ---------------------------------
     def unrolled_training_step(self, windows: Dict[str, Tensor], n_steps: int, through_state: bool = True,
-                               is_training: bool = True) -> Tuple[Tensor, Tensor]:
+                               is_training: bool = True, noise_draw=None, frame_ids=None) -> Tuple[Tensor, Tensor]:
         """Not in the reference, which trains on single steps only: the loss of an ``n_steps`` rollout unrolled under autograd, the
         remedy for rollout drift.  ``windows`` has the layout `rollout_batch` takes -- [W, T, N, .] series with T >= n_steps,
         `cells` and a `mesh_pos` shared by all windows given once -- and also holds the per-step series `get_target` reads
@@ -402,6 +436,10 @@ class AbstractSystemModel(nn.Module):
         construction and therefore also works for PlateModel and for models with a connector, which refuse ``through_state=True``
         with ``n_steps`` > 1 unless `position_gradients` is set (the gradient then holds the cluster labels, the world-edge
         membership and the spread winners of every step constant).  A configured graph balancer raises what expand_graph_batch raises.
+        ``noise_draw`` (None: no noise, the launches of before): frame 0 of the noise field (the state series) and frame 0 of its
+        `target|` series of all W windows are perturbed by ONE `add_noise` launch before step 0, with draw ``noise_draw``, the
+        model's `noise_seed`, and window w as frame ``frame_ids[w]`` (default w).  The targets of the later steps are untouched: only
+        step 0 holds dataset values, the reasoning that keeps the normalisers from accumulating there.
         -> (loss = the mean of the per-step losses, the per-step losses detached [n_steps]).  ``n_steps`` = 1 is `training_step` on
         the batched graph, bit for bit.
         Out of scope: HIP-graph capture of the unrolled step; the data-parallel trainer (parallel.Trainer.step keeps its single-step
@@ -417,13 +455,19 @@ class AbstractSystemModel(nn.Module):
         cells, mesh_pos = self._shared_mesh(windows)
         node_type = windows['node_type'][:, 0].to(device).to(torch.int64)
         W, N = node_type.shape[0], node_type.shape[1]
-        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type, ls.state: windows[ls.state][:, 0].to(device)}
+        first = {}                                                      # frame 0 of the series the noise replaces
+        if noise_draw is not None:
+            names = (self._params.get('field'), 'target|' + self._params.get('field'))
+            noisy = self.add_noise(dict({name: windows[name][:, 0] for name in names}, node_type=node_type), noise_draw, frame_ids)
+            first = {name: noisy[name] for name in names}
+        frame = {'cells': cells, 'mesh_pos': mesh_pos, 'node_type': node_type,
+                 ls.state: first.get(ls.state, windows[ls.state][:, 0]).to(device)}
         if ls.prev:
             frame[ls.prev] = windows[ls.prev][:, 0].to(device)
         losses = []
         for t in range(n_steps):
             for name in ls.per_step:
-                frame[name] = windows[name][:, t].to(device)
+                frame[name] = (first[name] if t == 0 and name in first else windows[name][:, t]).to(device)
             accumulate = bool(is_training) and t == 0
             graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate)
             flat = self.flatten_frames(frame)

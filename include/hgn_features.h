@@ -21,6 +21,7 @@
  *   rmp/hierarchical_connector.py:39-45  derivative of the cluster means         -> hgn_member_mean_bwd
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
  *                                                                              hgn_normalizer_update, hgn_normalize
+ *   data/preprocessing.py:84-98      Preprocessing._add_noise, per frame         -> hgn_training_noise (a batch of frames)
  */
 #ifndef HGN_FEATURES_H
 #define HGN_FEATURES_H
@@ -229,6 +230,34 @@ int hgn_rollout_advance_bwd(const float* d_next, int64_t ld_dnext, const float* 
                             float cp, const int64_t* node_type, int64_t ldt, uint32_t free_mask, int has_fallback,
                             int64_t rows, float* d_net, int64_t ld_dnet, float* d_cur, int64_t ld_dcur, float* d_prev,
                             int64_t ld_dprev, float* d_fallback, int64_t ld_dfb, void* stream);
+
+/* ---- seeded training noise for a batch of frames (src/data/preprocessing.py:84-98, Preprocessing._add_noise) -----------------
+ * What the reference does per frame with torch.normal, torch.where and two in-place additions -- a normal(0, std_) sample per
+ * element of frame[field], zeroed on every row whose node type is not free, added to the field and, scaled by (1 - gamma), to
+ * `target|field` -- for all frames of a batch in ONE launch, one thread per row, 256 threads per block, into fresh outputs.
+ * Plain vector loads and stores: no LDS, no atomics; equal bits on every run.
+ * x [rows, ldx], target (nullable) [rows, ld_tgt], out_x [rows, ld_ox], out_target (null iff target is) [rows, ld_ot]; d = 1..4
+ * columns; node_type int64 with element stride ldt.  The rows are rows / rows_per_frame frames of rows_per_frame nodes each.
+ * Generator: counter-based, so the sample of a row is a pure function of (seed, draw, frame id, node) and of nothing else -- not of
+ * the frame's place in the batch, not of the batch size, not of the process that holds the frame.  Row r has f = r / rows_per_frame,
+ * n = r % rows_per_frame and fid = frame_ids ? (uint32)frame_ids[f] : (uint32)f (frame_ids: device int64, one per frame).  It takes
+ * the four words w_0..w_3 of Philox4x32-10 with counter (n, fid, (uint32)draw, (uint32)(draw >> 32)), key ((uint32)seed,
+ * (uint32)(seed >> 32)), multipliers 0xD2511F53 / 0xCD9E8D57 and key increments 0x9E3779B9 / 0xBB67AE85 (Random123's constants
+ * and known answers).  Box-Muller in fp32 with the accurate logf / sqrtf / cosf / sinf: k_i = w_i >> 9, u1 = (k_0 + 0.5) 2^-23
+ * (exact, in (0, 1)), u2 = k_1 2^-23, rad = sqrtf(-2 logf(u1)), theta = 2 pi u2, z_0 = rad cosf(theta), z_1 = rad sinf(theta);
+ * z_2, z_3 likewise from w_2, w_3.  Column c uses z_c.
+ * A row is free when its type lies in [0, 32) and that bit of free_mask is set (the convention of hgn_rollout_advance).
+ *   free row:       nz = std_ * z_c;  out_x = x + nz;  out_target = target + target_scale * nz    (every product and sum rounded
+ *                                                                                                   on its own: no fma)
+ *   any other row:  out_x = x, out_target = target, copied bit for bit
+ * Every matrix has its own row stride; outputs must not overlap inputs; every output element is written exactly once.
+ * rows = 0: no-op.  HGN_E_INVALID before any launch: d outside 1..4, rows outside [0, 2^31), rows_per_frame < 1 or not dividing
+ * rows, a row stride smaller than d (ldt < 1), std_ negative or not finite, target and out_target not both null or both given,
+ * null x / node_type / out_x with rows > 0. */
+int hgn_training_noise(const float* x, int64_t ldx, int d, const int64_t* node_type, int64_t ldt, uint32_t free_mask,
+                       int64_t rows, int64_t rows_per_frame, const int64_t* frame_ids /* nullable */, uint64_t seed,
+                       uint64_t draw, float std_, const float* target /* nullable */, int64_t ld_tgt, float target_scale,
+                       float* out_x, int64_t ld_ox, float* out_target /* null iff target is */, int64_t ld_ot, void* stream);
 
 /* ---- backward of the connector's cluster mean (hierarchical_connector.py:39-45; rmp.py HierarchicalConnector.run, the line
  * `means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))`) ----------------------------------

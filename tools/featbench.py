@@ -9,7 +9,10 @@
     with the hetero connector per-frame expand_graph + batch_graphs against expand_graph_batch -- both paths in this process, on
     the same inputs.
 
-    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only]
+  * with --noise, the seeded training noise alone: one launch per batch of B = 21 / 128 flag frames against the reference's torch
+    sequence per frame (noise_timing).
+
+    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only | --noise]
 Prints one JSON object.
 """
 import argparse
@@ -95,15 +98,67 @@ def batched_builds():
     return out
 
 
+def noise_timing(rounds=20, warm=3):
+    """Training noise for B = 21 and B = 128 frames of the 1 600-node flag mesh: the one hgn_training_noise launch (FlagModel.add_noise
+    on the stacked frames) against the torch sequence of the reference's Preprocessing._add_noise (src/data/preprocessing.py:84-98)
+    run once per frame.  The two alternate in one process; every round of either is timed with device events of its own
+    (ms per batch, mean and min over the timed rounds)."""
+    from hgn_amd import synthetic, system_model
+    from hgn_amd.util import NodeType
+    cfg = dict(params('none', 16), field='world_pos', noise=0.003, gamma=0.9)
+    model = system_model.FlagModel(cfg)
+    model.noise_seed = 1
+    field, scale, gamma = cfg['field'], cfg['noise'], cfg['gamma']
+    host = [synthetic.flag_frame(seed=i, nx=40, ny=40) for i in range(4)]
+    normal = torch.tensor([NodeType.NORMAL.value], device='cuda').int()
+
+    def per_frame(frame):
+        noise = torch.normal(torch.zeros(frame[field].size(), dtype=torch.float32, device='cuda'), std=scale)
+        rows = torch.eq(frame['node_type'], normal)[:, 0]
+        mask = torch.stack([rows for _ in range(noise.shape[1])], dim=1)
+        noise = torch.where(mask, noise, torch.zeros_like(noise))
+        frame[field] += noise
+        frame['target|' + field] += (1.0 - gamma) * noise
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    out = {}
+    for B in (21, 128):
+        names = (field, 'target|' + field, 'node_type')
+        frames = [{k: host[i % 4][k].cuda().clone() for k in names} for i in range(B)]          # written in place by the torch sequence
+        stacked = {k: torch.stack([host[i % 4][k] for i in range(B)]).cuda() for k in names}
+        draws = iter(range(10 ** 6))
+        ms = {'one launch': [], 'torch sequence per frame': []}
+        for r in range(warm + rounds):
+            one = timed(lambda: model.add_noise(stacked, next(draws)))
+            seq = timed(lambda: [per_frame(f) for f in frames])
+            if r >= warm:
+                ms['one launch'].append(one)
+                ms['torch sequence per frame'].append(seq)
+        out[f'B={B}'] = {'nodes per frame': int(stacked[field].shape[1]),
+                         **{f'{k} ms {stat}': fn(v) for k, v in ms.items() for stat, fn in (('mean', lambda v: sum(v) / len(v)), ('min', min))}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=50)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--batched-only', action='store_true', help='only the per-frame against batched build / expand comparison')
+    ap.add_argument('--noise', action='store_true', help='only the training noise: one launch per batch against the torch sequence per frame')
     a = ap.parse_args()
     from hgn_amd import features, synthetic, system_model
     from hgn_amd.normalizer import Normalizer
     res = {}
+    if a.noise:
+        print(json.dumps({'training noise': noise_timing()}))
+        return
     if a.batched_only:
         print(json.dumps({'batched builds': batched_builds()}))
         return
