@@ -577,6 +577,89 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
 }
 __global__ void step_incr_kernel(int* step) { *step += 1; }
 
+// Global-norm clipping of the flat gradient (hgn_grad_clip_coef) and the Adam update that applies it (hgn_adam_step_clip).
+// The sum of squares is DETERMINISTIC: a fixed grid of CLIP_GRID x CLIP_BLOCK threads, thread T always owns the elements
+// T, T + CLIP_GRID * CLIP_BLOCK, ... (scalar loads: no head / tail that would depend on the buffer's alignment), every square and
+// every partial sum is a double, and partials meet in a fixed order (lanes by halving strides, waves 0..3, workgroups by halving
+// strides) -- no atomics.  Squares of fp32 numbers cannot overflow a double, so the sum is non-finite exactly when an entry is.
+constexpr int CLIP_GRID = 512;                    // two workgroups per CU; 4 B per parameter read once (~10 MB for the 15-block model)
+constexpr int CLIP_BLOCK = 256;
+__device__ __forceinline__ double clip_block_sum(double s, double* lds) {
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[wave] = s;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);    // (every thread: only thread 0's copy is used)
+}
+__global__ __launch_bounds__(CLIP_BLOCK) void grad_sqsum_kernel(const float* __restrict__ g, long n, double* __restrict__ part) {
+  __shared__ double lds[CLIP_BLOCK / 64];
+  const long stride = (long)CLIP_GRID * CLIP_BLOCK;
+  long i = (long)blockIdx.x * CLIP_BLOCK + threadIdx.x;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (; i + 3 * stride < n; i += 4 * stride) {     // four loads in flight per thread
+    const double a = (double)g[i], b = (double)g[i + stride], c = (double)g[i + 2 * stride], d = (double)g[i + 3 * stride];
+    s0 += a * a; s1 += b * b; s2 += c * c; s3 += d * d;
+  }
+  for (; i < n; i += stride) { const double a = (double)g[i]; s0 += a * a; }
+  const double s = clip_block_sum((s0 + s1) + (s2 + s3), lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// One workgroup: sum of the CLIP_GRID partials -> stats = [norm, coef], and the step / skip counters (the job of step_incr_kernel
+// on this path).  coef = min(1, max_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_ forms it, in double; max_norm <= 0:
+// no clipping.  A non-finite sum with `skip`: coef = 0 (hgn_adam_step_clip then stores nothing), *skipped += 1, *step stays.
+__global__ __launch_bounds__(CLIP_BLOCK) void grad_clip_finalise_kernel(const double* __restrict__ part, double max_norm, int skip,
+                                                                        float* __restrict__ stats, int* step, int* skipped) {
+  __shared__ double lds[CLIP_BLOCK];
+  double s = 0.0;
+  for (int k = threadIdx.x; k < CLIP_GRID; k += CLIP_BLOCK) s += part[k];
+  lds[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = CLIP_BLOCK / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) lds[threadIdx.x] += lds[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double sum = lds[0];
+  const double norm = sqrt(sum);
+  float coef = 1.0f;
+  if (max_norm > 0.0) {
+    const double c = max_norm / (norm + 1e-6);
+    coef = c < 1.0 ? (float)c : 1.0f;
+  }
+  const bool bad = skip && !isfinite(sum);
+  if (bad) {
+    coef = 0.0f;
+    if (skipped) *skipped += 1;
+  } else if (step) {
+    *step += 1;
+  }
+  stats[0] = (float)norm;
+  stats[1] = coef;
+}
+// adam_dev_kernel with the gradient scaled by grad_scale * *coef (the product of the two scalars first, in fp32) and *step read as
+// it is: hgn_grad_clip_coef has counted the step.  A coefficient of exactly 0 (a skipped step) returns before any store.
+__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                 const int* __restrict__ step, float grad_scale, const float* __restrict__ coef_dev) {
+  __shared__ float bc[2];
+  const float coef = *coef_dev;
+  if (coef == 0.0f) return;
+  if (threadIdx.x == 0) {
+    const double t = (double)(*step);
+    bc[0] = (float)(1.0 - pow((double)b1, t));
+    bc[1] = (float)sqrt(1.0 - pow((double)b2, t));
+  }
+  __syncthreads();
+  const float gscale = grad_scale * coef;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float gi = g[i] * gscale;
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi; v[i] = vi;
+  p[i] -= (lr / bc[0]) * (mi / (sqrtf(vi) / bc[1] + eps));
+}
+
 constexpr int WG_CHUNKS = 512;                    // workgroups of one weight-gradient launch: two per CU (768 = three per CU measured no faster; wgrad6s_kernel is built for two)
 static int chunks_mfma(long M, int n_tasks) {
   long c = WG_CHUNKS / (n_tasks > 0 ? n_tasks : 1);
@@ -748,4 +831,38 @@ extern "C" int hgn_adam_step_dev(float* p, const float* g, float* m, float* v, i
   hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
                      beta1, beta2, eps, step_dev, grad_scale);
   return hgn_check_launch("hgn_adam_step_dev");
+}
+
+extern "C" int hgn_grad_clip_workspace_bytes(int64_t n, size_t* bytes) {
+  if (!bytes || n < 0) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_workspace_bytes: bad argument");
+  *bytes = (size_t)CLIP_GRID * sizeof(double);      // one partial per workgroup of the fixed grid, whatever n is
+  return HGN_OK;
+}
+
+extern "C" int hgn_grad_clip_coef(const float* g, int64_t n, float max_norm, int skip_nonfinite, float* stats, int32_t* step_dev,
+                                  int32_t* skipped_dev, void* ws, size_t ws_bytes, void* stream) {
+  if (n < 0) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: n < 0");
+  if (!g && n > 0) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: null gradient");
+  if (!stats) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: null stats");
+  if (!ws || ((uintptr_t)ws & 7)) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: null or misaligned workspace");
+  if (ws_bytes < (size_t)CLIP_GRID * sizeof(double))
+    return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: workspace too small (hgn_grad_clip_workspace_bytes)");
+  if (max_norm != max_norm) return hgn_fail(HGN_E_INVALID, "hgn_grad_clip_coef: max_norm is NaN");
+  ProfScope ps(9, (double)n, (hipStream_t)stream);
+  hipLaunchKernelGGL(grad_sqsum_kernel, dim3(CLIP_GRID), dim3(CLIP_BLOCK), 0, (hipStream_t)stream, g, (long)n, (double*)ws);
+  hipLaunchKernelGGL(grad_clip_finalise_kernel, dim3(1), dim3(CLIP_BLOCK), 0, (hipStream_t)stream, (const double*)ws, (double)max_norm,
+                     skip_nonfinite ? 1 : 0, stats, step_dev, skipped_dev);
+  return hgn_check_launch("hgn_grad_clip_coef");
+}
+
+extern "C" int hgn_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                  float eps, const int32_t* step_dev, float grad_scale, const float* coef_dev, void* stream) {
+  if (!step_dev) return hgn_fail(HGN_E_INVALID, "hgn_adam_step_clip: null step counter");
+  if (!coef_dev) return hgn_fail(HGN_E_INVALID, "hgn_adam_step_clip: null coefficient");
+  if (n == 0) return HGN_OK;
+  if (!p || !g || !m || !v || n < 0) return hgn_fail(HGN_E_INVALID, "hgn_adam_step_clip: bad argument");
+  ProfScope ps(9, (double)n, (hipStream_t)stream);
+  hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
+                     beta1, beta2, eps, step_dev, grad_scale, coef_dev);
+  return hgn_check_launch("hgn_adam_step_clip");
 }

@@ -160,6 +160,11 @@ _SIGS = {
                                 C.c_float, C.c_float, C.c_int32, C.c_float, C.c_void_p]),
     'hgn_adam_step_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                     C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
+    'hgn_grad_clip_workspace_bytes': (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    'hgn_grad_clip_coef': (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    'hgn_adam_step_clip': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
+                                     C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     # include/hgn_features.h
     'hgn_cells_to_edges_workspace_bytes': (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
     'hgn_cells_to_edges': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),

@@ -1533,6 +1533,64 @@ def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, step_dev, grad_scale=1.0):
                                             eps, step_dev.data_ptr(), grad_scale, _lib.stream_ptr()), 'hgn_adam_step_dev')
 
 
+def _check_flat(what, *tensors):
+    for t in tensors:
+        _lib.require_gpu(t)
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise _lib.HgnError(f'{what} needs contiguous fp32 flat buffers')
+
+
+def _check_counter(what, name, t, device):
+    if t is None:
+        return
+    _lib.require_gpu(t)
+    if t.dtype != torch.int32 or t.numel() != 1 or t.device != device:
+        raise _lib.HgnError(f'{what}: {name} must be a one-element int32 tensor on the gradient\'s device')
+
+
+def grad_norm_clip(g, max_norm, stats=None, step_dev=None, skipped_dev=None, skip_nonfinite=False):
+    """Global-norm clipping coefficient of the flat gradient ``g``, on the device (include/hgn_mp.h: hgn_grad_clip_coef; two
+    launches, no host read: capturable).  -> ``stats`` (fp32 [2], made if None) = [norm of g, coef = min(1, max_norm / (norm +
+    1e-6))] -- torch.nn.utils.clip_grad_norm_'s formula; ``max_norm`` None or <= 0: no clipping, coef 1, the norm is still
+    reported.  ``g`` is not changed: `adam_step_clip` applies the coefficient.  ``step_dev`` (the Adam step counter) is
+    incremented, unless ``skip_nonfinite`` is set and g holds an inf or a NaN: then coef = 0, ``skipped_dev`` is incremented and
+    the step counter stays.  The sum of squares is formed in double in a fixed order: two calls give the same bits, whatever the
+    buffer's alignment."""
+    what = 'grad_norm_clip'
+    _check_flat(what, g)
+    if stats is None:
+        stats = torch.empty(2, dtype=torch.float32, device=g.device)
+    _check_flat(what, stats)
+    if stats.numel() != 2 or stats.device != g.device:
+        raise _lib.HgnError('grad_norm_clip: stats must be a two-element fp32 tensor on the gradient\'s device')
+    _check_counter(what, 'step_dev', step_dev, g.device)
+    _check_counter(what, 'skipped_dev', skipped_dev, g.device)
+    nbytes = C.c_size_t(0)
+    _lib.check(_lib.lib().hgn_grad_clip_workspace_bytes(g.numel(), C.byref(nbytes)), 'hgn_grad_clip_workspace_bytes')
+    ws = _workspace(g.device, nbytes.value, 'grad_clip')
+    _lib.check(_lib.lib().hgn_grad_clip_coef(g.data_ptr(), g.numel(), 0.0 if max_norm is None else float(max_norm),
+                                             1 if skip_nonfinite else 0, stats.data_ptr(),
+                                             step_dev.data_ptr() if step_dev is not None else None,
+                                             skipped_dev.data_ptr() if skipped_dev is not None else None,
+                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'hgn_grad_clip_coef')
+    return stats
+
+
+def adam_step_clip(p, g, m, v, lr, b1, b2, eps, step_dev, coef, grad_scale=1.0):
+    """`adam_step_dev`'s update on the gradient times (grad_scale * coef[0]), with ``coef`` a device tensor (`grad_norm_clip`'s
+    stats[1:2]) and ``step_dev`` read as it is: `grad_norm_clip` has counted the step.  A coefficient of exactly 0 (a skipped
+    step) leaves p, m and v untouched."""
+    what = 'adam_step_clip'
+    _check_flat(what, p, g, m, v, coef)
+    if not (p.numel() == g.numel() == m.numel() == v.numel()) or coef.numel() != 1 or any(t.device != p.device for t in (g, m, v, coef)):
+        raise _lib.HgnError('adam_step_clip: p, g, m, v must have one size and device; coef is one fp32 element on that device')
+    if step_dev is None:
+        raise _lib.HgnError('adam_step_clip: step_dev is required')
+    _check_counter(what, 'step_dev', step_dev, p.device)
+    _lib.check(_lib.lib().hgn_adam_step_clip(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1, b2, eps,
+                                             step_dev.data_ptr(), grad_scale, coef.data_ptr(), _lib.stream_ptr()), 'hgn_adam_step_clip')
+
+
 def prof_enable(on: bool):
     _lib.check(_lib.lib().hgn_prof_enable(1 if on else 0))
 

@@ -174,12 +174,23 @@ class DataParallelTrainer:
     that the ranges hold about equal numbers of parameters; range k is all-reduced (asynchronously: RCCL's own stream, after
     the gradient kernels enqueued so far) from an autograd node at its boundary, while the backward pass goes on through the
     earlier layers.  The range of the first parameters goes last, after ``backward()`` has returned, and carries the node
-    count.  The result is the same sum as one all-reduce of the whole buffer (every element is reduced exactly once)."""
+    count.  The result is the same sum as one all-reduce of the whole buffer (every element is reduced exactly once).
+
+    ``max_grad_norm``: clip the gradient of the global-mean loss by its global norm (torch.nn.utils.clip_grad_norm_'s formula)
+    before Adam; ``skip_nonfinite``: a step whose gradient holds an inf or a NaN changes neither the parameters, nor m, v, nor
+    the step count.  Both are device-side parts of the step, after the collective and the global-mean scaling
+    (ops.grad_norm_clip -> ops.adam_step_clip: no host read, so a captured step keeps them), computed by every rank from the
+    same all-reduced bits with a deterministic kernel: replicas stay bit-equal.  Either one puts the Adam step counter on the
+    device (`t_dev`, created if ``device_step`` is off).  `grad_stats` ([norm, coef] of the last step) and `skipped_dev` (the
+    number of skipped steps) are device tensors the trainer never reads: a caller logs them when it wants.  With both unset the
+    step is launch for launch what it is without them.  On the device the clipped update is the library's own kernel, as with
+    ``device_step``; an ``adam_fn`` is called for CPU tensors only (with the coefficient as its ``grad_scale``), and
+    ``skip_nonfinite`` refuses any but `_torch_adam`."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  group: Optional[dist.ProcessGroup] = None, adam_fn: Optional[Callable] = None,
                  device_step: bool = False, wgrad_stream: bool = False, buckets: int = 4, bucket_after=None,
-                 force_collectives: bool = False):
+                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self.model = model
         from . import ops as _ops
         self.ctx = getattr(model, '_hgn_ctx', None) or _ops.default_context()      # the launch context of the model it trains (ops.Context)
@@ -196,6 +207,20 @@ class DataParallelTrainer:
         self.t = 0
         # device-resident step counter: needed when step() is captured into a HIP graph (graphs.GraphedTrainStep)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=self.fp.flat.device) if device_step else None
+        # clipping by the global norm / skipping a non-finite step: device-side parts of the step (class docstring)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.clip = self.max_grad_norm is not None or self.skip_nonfinite
+        if self.skip_nonfinite and adam_fn is not None and adam_fn is not _torch_adam:
+            raise ValueError('skip_nonfinite needs the trainer\'s own update (a skipped step must leave p, m and v untouched): '
+                             'no adam_fn other than parallel._torch_adam')
+        self.grad_stats = self.skipped_dev = None
+        if self.clip:
+            dev = self.fp.flat.device
+            if self.t_dev is None:                                   # the skip decision is made on the device: so is the step count
+                self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.grad_stats = torch.zeros(2, dtype=torch.float32, device=dev)      # [norm, coef] of the last step; never read here
+            self.skipped_dev = torch.zeros(1, dtype=torch.int32, device=dev)       # steps skipped as non-finite
         if adam_fn is None:
             from . import ops
             adam_fn = ops.adam_step
@@ -281,6 +306,59 @@ class DataParallelTrainer:
             torch.cuda.current_stream().wait_stream(self.side)      # join: all weight gradients are in the flat buffer
         return self.reduce_and_update(sq.detach(), out.shape[1])
 
+    def step_unrolled(self, system_model, windows, n_steps: int, through_state: bool = True, is_training: bool = True,
+                      noise_draw=None, frame_ids=None):
+        """One optimiser step on the loss of an ``n_steps`` rollout unrolled under autograd
+        (`system_model.unrolled_training_step`, whose arguments these are) with everything `step` gives a single step: the flat
+        gradient buffer the kernels accumulate into, the all-reduce, the global-mean scaling, clipping and the fused Adam.
+        ``system_model.learned_model`` must be this trainer's model.  ``windows`` are THIS RANK's windows: the caller shards them
+        (`shard_indices`) and passes their global ids as ``frame_ids``, so that with ``noise_draw`` every window gets the noise
+        sample a single process gives it; normaliser statistics are shared through `attach_normalizer_sync`.
+        The loss is the mean over the free rows (`_loss_mask`: the same rows at every step) of this rank's W * N rows; the rank
+        back-propagates loss * count with count = its number of free rows, which rides in the count slot, so that after the
+        collective  sum_r(count_r * grad loss_r) / sum_r count_r  is the gradient of the mean over ALL windows, for any shard sizes.
+        -> (this rank's share loss_r * count_r / sum count of that global mean, the per-step losses of this rank's windows).
+        Collectives: the bucket hooks would fire once per network call, and a range may only leave after the LAST backward visit
+        of its boundary; this step therefore runs with `overlap` off -- ONE collective over the whole buffer after backward(), as
+        the captured path does -- and restores the setting.
+        Packed weight images: the weights do not change inside the step and every network call asks for the same images.  The
+        recording step (ops.begin_step_packs without a plan) sees every (MLP, form) pair n_steps times, PackPlan keeps each once;
+        in later steps the plan's one launch refreshes them all before the first call and sets `plan_epoch`, after which every
+        packs_of of the step -- calls 2 .. n_steps included -- finds its cached image under an unchanged key.  A plan recorded by
+        `step` serves this method and the other way round (the same MLPs).
+        Out of scope: HIP-graph capture of the unrolled step; a graph balancer; meshes that differ within a batch; activation
+        checkpointing."""
+        if getattr(system_model, 'learned_model', None) is not self.model:
+            raise ValueError('step_unrolled: system_model.learned_model is not the model this trainer was built on')
+        self.fp.check_outsiders()
+        self.fp.zero_grad()
+        self._pending, self._done_upto = [], None
+        cuda = self.fp.flat.is_cuda
+        if cuda:
+            from . import ops
+            ops.discard_stale_wgrad(self.ctx)
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream())
+            self.ctx.wgrad_stream = self.side
+        node_type = windows['node_type'][:, 0]
+        count = system_model._loss_mask({'node_type': node_type.reshape(-1, node_type.shape[-1])}).sum().to(torch.float32).reshape(1)
+        self.fp.count.copy_(count)
+        overlap, self.overlap = self.overlap, False
+        try:
+            if cuda:
+                ops.begin_step_packs(self.ctx)
+            loss, per_step = system_model.unrolled_training_step(windows, n_steps, through_state=through_state, is_training=is_training,
+                                                                 noise_draw=noise_draw, frame_ids=frame_ids)
+            (loss * count).backward()           # (`count`, not the slot: the slot shares its version counter with the gradients)
+        finally:
+            self.overlap = overlap
+            if cuda:
+                ops.end_step_packs(self.ctx)
+            if self.side is not None:
+                self.ctx.wgrad_stream = None
+                torch.cuda.current_stream().wait_stream(self.side)
+        return self.reduce_and_update(loss.detach() * count, 1), per_step
+
     def reduce_and_update(self, sq_local: torch.Tensor, width: int) -> torch.Tensor:
         """[local NORMAL-node count | gradients of the local squared-error sum] -> all-reduce (the ranges not yet under way; with
         nothing under way -- captured backward pass -- ONE collective over the whole buffer) -> scale to the gradient of the global mean (flag.py:150-152
@@ -295,7 +373,9 @@ class DataParallelTrainer:
         inv = 1.0 / (self.fp.count * width)
         self.fp.grad.mul_(inv)
         self.t += 1
-        if self.t_dev is not None:
+        if self.clip:
+            self._clipped_update()
+        elif self.t_dev is not None:
             from . import ops
             ops.adam_step_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t_dev)
         else:
@@ -304,6 +384,32 @@ class DataParallelTrainer:
             from . import ops
             self.ctx.invalidate_packs()             # the Adam kernel rewrote the parameters behind torch's version counters
         return (sq_local * inv).squeeze(0)
+
+    def _clipped_update(self):
+        """norm of the global-mean gradient -> [norm, coef] in `grad_stats`, step / skip counters -> Adam on coef * gradient.
+        On the device two launches and one (ops.grad_norm_clip, ops.adam_step_clip), no host read; CPU tensors (the gloo host
+        tests) take the same arithmetic in torch: the norm in fp64, clip_grad_norm_'s coefficient, the skip."""
+        fp, (b1, b2) = self.fp, self.betas
+        if fp.flat.is_cuda:
+            from . import ops
+            with ops.using(self.ctx):
+                ops.grad_norm_clip(fp.grad, self.max_grad_norm, self.grad_stats, self.t_dev, self.skipped_dev, self.skip_nonfinite)
+            ops.adam_step_clip(fp.flat, fp.grad, self.m, self.v, self.lr, b1, b2, self.eps, self.t_dev, self.grad_stats[1:2])
+            return
+        total = fp.grad.double().square().sum()
+        norm = total.sqrt()
+        coef = 1.0
+        if self.max_grad_norm is not None and self.max_grad_norm > 0:
+            c = self.max_grad_norm / (float(norm) + 1e-6)
+            coef = float(torch.tensor(c, dtype=torch.float32)) if c < 1.0 else 1.0
+        if self.skip_nonfinite and not bool(torch.isfinite(total)):
+            coef = 0.0
+            self.skipped_dev += 1
+        else:
+            self.t_dev += 1
+        self.grad_stats[0], self.grad_stats[1] = norm.to(torch.float32), coef
+        if coef != 0.0:
+            self.adam_fn(fp.flat, fp.grad, self.m, self.v, self.lr, b1, b2, self.eps, int(self.t_dev), grad_scale=coef)
 
 
 def attach_normalizer_sync(normalizers: Iterable, group: Optional[dist.ProcessGroup] = None):

@@ -399,8 +399,9 @@ class AbstractSystemModel(nn.Module):
         entry is the same object (the flag's `prev|world_pos` is untouched, as in the reference) and the inputs are not written.  A
         scale of 0, or a `model` section without `noise`, returns the copy without a launch.
         Out of scope: the connector's `hyper_noise` keeps torch.normal; the reference's own src/data/preprocessing.py path through
-        the shim is unchanged; noise inside captured graphs; parallel.DataParallelTrainer is untouched (a rank calls this with its
-        own frame ids before it builds its shard)."""
+        the shim is unchanged; noise inside captured graphs.  (parallel.DataParallelTrainer.step_unrolled hands a rank's global
+        window ids through `unrolled_training_step` to this method; before a single-step `step` a rank calls it itself, with its
+        own frame ids, before it builds its shard.)"""
         out = dict(frames)
         scale = self._params.get('noise')
         if not scale:
@@ -442,8 +443,9 @@ class AbstractSystemModel(nn.Module):
         step 0 holds dataset values, the reasoning that keeps the normalisers from accumulating there.
         -> (loss = the mean of the per-step losses, the per-step losses detached [n_steps]).  ``n_steps`` = 1 is `training_step` on
         the batched graph, bit for bit.
-        Out of scope: HIP-graph capture of the unrolled step; the data-parallel trainer (parallel.Trainer.step keeps its single-step
-        loss; this method returns an ordinary loss for any optimiser); activation checkpointing; meshes that differ within a batch."""
+        This method returns an ordinary loss for any optimiser; parallel.DataParallelTrainer.step_unrolled takes it through the
+        project's own trainer (flat gradient buffer, all-reduce to the mean over all ranks' windows, `max_grad_norm`, fused Adam).
+        Out of scope: HIP-graph capture of the unrolled step; activation checkpointing; meshes that differ within a batch."""
         ls = self._LOCKSTEP
         n_steps = int(n_steps)
         if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (ls.state,) + ls.per_step):

@@ -420,6 +420,23 @@ int hgn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
  * call can be captured once into a HIP graph and replayed (a host-side step would be frozen at capture time). */
 int hgn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                       float eps, int32_t* step_dev, float grad_scale, void* stream);
+/* Clipping by the global norm, and a guard against a non-finite step, as device-side parts of the step (stream-ordered, no host
+ * read: capturable).  hgn_grad_clip_coef writes stats[0] = (float)sqrt(sum g[i]^2) and stats[1] = coef, where
+ * c = max_norm / (norm + 1e-6) in double and coef = c < 1 ? (float)c : 1 (torch.nn.utils.clip_grad_norm_); max_norm <= 0: no
+ * clipping, coef = 1, the norm is still reported.  The sum is deterministic: a fixed grid with a fixed assignment of elements
+ * to threads (independent of g's alignment), squares and partial sums in double, combined in a fixed order, no atomics.
+ * skip_nonfinite != 0 and a non-finite sum (an inf or a NaN in g): coef = 0, *skipped_dev += 1, *step_dev is NOT incremented;
+ * otherwise *step_dev += 1 (both counters may be null).  Without skip_nonfinite the formula stands as it is (an infinite norm
+ * gives coef 0, a NaN norm coef 1).  `ws`: 8-byte aligned scratch of hgn_grad_clip_workspace_bytes bytes.  n = 0 is valid
+ * (norm 0, coef 1; g may then be null).
+ * hgn_adam_step_clip is hgn_adam_step_dev's update with *step_dev read as it is (hgn_grad_clip_coef counted the step) and
+ * every gradient entry multiplied by (grad_scale * *coef_dev), that product formed first in fp32; a coefficient of exactly 0
+ * leaves p, m and v untouched. */
+int hgn_grad_clip_workspace_bytes(int64_t n, size_t* bytes);
+int hgn_grad_clip_coef(const float* g, int64_t n, float max_norm, int skip_nonfinite, float* stats /*[2]*/, int32_t* step_dev,
+                       int32_t* skipped_dev, void* ws, size_t ws_bytes, void* stream);
+int hgn_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                       float eps, const int32_t* step_dev, float grad_scale, const float* coef_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line).
