@@ -10,6 +10,8 @@
 //   wgrad_dma_kernel plain fp32 MFMAs from an LDS-DMA ring (HGN_FP32_MFMA=1)
 //   wgrad_kernel     register-staged fp32 fallback for narrow / gathered operands (encoder inputs) and LayerNorm-affine tasks
 #include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include "hgn_host.h"
 #include "split_bf16.h"
@@ -660,6 +662,89 @@ __global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict_
   p[i] -= (lr / bc[0]) * (mi / (sqrtf(vi) / bc[1] + eps));
 }
 
+// The learning rate of step t (1-based) under a schedule (include/hgn_mp.h), in double.  The ONE statement of the formula:
+// hgn_lr_at calls it on the host, adam_sched_kernel on the device.  No contraction: both sides round every operation alike, and
+// differ by pow's last bits alone.  decay_steps == 0: the bracket is lr itself, so a constant schedule gives (double)lr exactly.
+__host__ __device__ inline double hgn_sched_lr(const hgn_adam_sched_t& s, int t) {
+#pragma clang fp contract(off)
+  const double lr = (double)s.lr, lr_min = (double)s.lr_min;
+  double rate = lr;
+  if (s.decay_steps > 0) {
+    const int past = t - s.warmup_steps;
+    rate = lr_min + (lr - lr_min) * pow((double)s.decay_rate, (double)(past > 0 ? past : 0) / (double)s.decay_steps);
+  }
+  if (s.warmup_steps > 0 && t < s.warmup_steps) rate = ((double)t / (double)s.warmup_steps) * rate;
+  return rate;
+}
+// adam_dev_kernel / adam_clip_kernel with the rate of the step formed from *step like the bias corrections: thread 0 of every
+// workgroup computes the same doubles (nothing reduced, no atomics).  The update keeps their fp32 expression; the decay factor
+// (1 - lr_t * weight_decay, rounded once) multiplies p only where it applies and is skipped otherwise, so that a constant schedule
+// without decay has the bits of those kernels.  coef_dev == nullptr: gscale = grad_scale (adam_dev_kernel); else grad_scale * coef
+// with a coefficient of exactly 0 returning before any store (adam_clip_kernel), lr_out included.
+constexpr int SCHED_BLOCK = 256, SCHED_PER_THREAD = 4;
+__global__ __launch_bounds__(SCHED_BLOCK) void adam_sched_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n, hgn_adam_sched_t s,
+    float b1, float b2, float eps, const int* __restrict__ step, float grad_scale, const float* __restrict__ coef_dev,
+    const uint8_t* __restrict__ decay_mask, float* __restrict__ lr_out) {
+  __shared__ float bc[4];
+  float gscale = grad_scale;
+  if (coef_dev) {
+    const float coef = *coef_dev;
+    if (coef == 0.0f) return;
+    gscale = grad_scale * coef;
+  }
+  // Each thread owns SCHED_PER_THREAD elements, SCHED_BLOCK apart (coalesced), and asks for them BEFORE thread 0 forms the
+  // scalars: the three pows in double (one more than adam_dev_kernel's) then run under the loads' latency, and a workgroup pays
+  // for them once per 1024 elements (at one element per thread and the loads behind the barrier a moving schedule cost 6 us of
+  // 18 on the 15-block model's buffer).
+  const bool decays = s.weight_decay > 0.f;
+  const long base = (long)blockIdx.x * (SCHED_BLOCK * SCHED_PER_THREAD) + threadIdx.x;
+  float gv[SCHED_PER_THREAD], mv[SCHED_PER_THREAD], vv[SCHED_PER_THREAD], pv[SCHED_PER_THREAD];
+  bool dk[SCHED_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < SCHED_PER_THREAD; ++k) {
+    const long i = base + (long)k * SCHED_BLOCK;
+    gv[k] = mv[k] = vv[k] = pv[k] = 0.f;
+    dk[k] = false;
+    if (i < n) {
+      gv[k] = g[i]; mv[k] = m[i]; vv[k] = v[i]; pv[k] = p[i];
+      dk[k] = decays && (!decay_mask || decay_mask[i]);
+    }
+  }
+  if (threadIdx.x == 0) {
+    const int ti = *step;
+    const double t = (double)ti;
+    const double lr_t = hgn_sched_lr(s, ti);
+    bc[0] = (float)(1.0 - pow((double)b1, t));
+    bc[1] = (float)sqrt(1.0 - pow((double)b2, t));
+    bc[2] = (float)lr_t;
+    bc[3] = (float)(1.0 - lr_t * (double)s.weight_decay);
+    if (lr_out && blockIdx.x == 0) *lr_out = (float)lr_t;
+  }
+  __syncthreads();
+  // The roundings are spelt out (no contraction; the one fused operation by name) as the compiler places them in those two
+  // kernels: products and sum of m and of v rounded one by one, p - step * quotient fused.  Left to the compiler they moved with
+  // the control flow around them (a decay branch turned the sums of m and v into fused ones).
+  const float lr = bc[2];
+#pragma unroll
+  for (int k = 0; k < SCHED_PER_THREAD; ++k) {
+    const long i = base + (long)k * SCHED_BLOCK;
+    if (i >= n) break;
+    float mi, vi, quot;
+    {
+#pragma clang fp contract(off)
+      const float gi = gv[k] * gscale;
+      mi = b1 * mv[k] + (1.f - b1) * gi;
+      vi = b2 * vv[k] + (1.f - b2) * gi * gi;
+      quot = mi / (sqrtf(vi) / bc[1] + eps);
+    }
+    m[i] = mi; v[i] = vi;
+    float pi = pv[k];
+    if (dk[k]) pi = pi * bc[3];
+    p[i] = fmaf(-(lr / bc[0]), quot, pi);
+  }
+}
+
 constexpr int WG_CHUNKS = 512;                    // workgroups of one weight-gradient launch: two per CU (768 = three per CU measured no faster; wgrad6s_kernel is built for two)
 static int chunks_mfma(long M, int n_tasks) {
   long c = WG_CHUNKS / (n_tasks > 0 ? n_tasks : 1);
@@ -865,4 +950,45 @@ extern "C" int hgn_adam_step_clip(float* p, const float* g, float* m, float* v, 
   hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
                      beta1, beta2, eps, step_dev, grad_scale, coef_dev);
   return hgn_check_launch("hgn_adam_step_clip");
+}
+
+// -> nullptr, or what is wrong with the schedule (shared by hgn_lr_at and hgn_adam_step_sched: checked before any launch)
+static const char* sched_fault(const hgn_adam_sched_t* s) {
+  if (!s) return "null schedule";
+  if (!std::isfinite(s->lr) || s->lr < 0.f) return "lr must be finite and >= 0";
+  if (!(s->lr_min >= 0.f && s->lr_min <= s->lr)) return "lr_min must lie in [0, lr]";
+  if (s->warmup_steps < 0 || s->decay_steps < 0) return "warmup_steps and decay_steps must be >= 0";
+  if (!(s->decay_rate > 0.f && s->decay_rate <= 1.f)) return "decay_rate must lie in (0, 1]";
+  if (!std::isfinite(s->weight_decay) || s->weight_decay < 0.f) return "weight_decay must be finite and >= 0";
+  if ((double)s->lr * (double)s->weight_decay >= 1.0) return "lr * weight_decay must be < 1";
+  return nullptr;
+}
+static int sched_fail(const char* fn, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", fn, what);
+  return hgn_fail(HGN_E_INVALID, msg);
+}
+
+extern "C" int hgn_lr_at(const hgn_adam_sched_t* s, int32_t step, double* lr) {
+  if (!lr) return sched_fail("hgn_lr_at", "null result pointer");
+  if (const char* bad = sched_fault(s)) return sched_fail("hgn_lr_at", bad);
+  if (step < 1) return sched_fail("hgn_lr_at", "step < 1 (Adam counts its steps from 1)");
+  *lr = hgn_sched_lr(*s, step);
+  return HGN_OK;
+}
+
+extern "C" int hgn_adam_step_sched(float* p, const float* g, float* m, float* v, int64_t n, const hgn_adam_sched_t* s, float beta1,
+                                   float beta2, float eps, int32_t* step_dev, int count_step, float grad_scale, const float* coef_dev,
+                                   const uint8_t* decay_mask, float* lr_out, void* stream) {
+  if (n < 0) return sched_fail("hgn_adam_step_sched", "n < 0");
+  if (n > 0 && (!p || !g || !m || !v)) return sched_fail("hgn_adam_step_sched", "null p, g, m or v");
+  if (!step_dev) return sched_fail("hgn_adam_step_sched", "null step counter");
+  if (const char* bad = sched_fault(s)) return sched_fail("hgn_adam_step_sched", bad);
+  if (count_step) hipLaunchKernelGGL(step_incr_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
+  if (n == 0) return count_step ? hgn_check_launch("hgn_adam_step_sched") : HGN_OK;
+  ProfScope ps(9, (double)n, (hipStream_t)stream);
+  const int64_t per_block = (int64_t)SCHED_BLOCK * SCHED_PER_THREAD;
+  hipLaunchKernelGGL(adam_sched_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SCHED_BLOCK), 0, (hipStream_t)stream, p, g, m, v, (long)n, *s,
+                     beta1, beta2, eps, (const int*)step_dev, grad_scale, coef_dev, decay_mask, lr_out);
+  return hgn_check_launch("hgn_adam_step_sched");
 }

@@ -94,6 +94,12 @@ class Pack(C.Structure):
                 ('out', C.c_void_p)]
 
 
+class AdamSched(C.Structure):
+    """hgn_adam_sched_t (include/hgn_mp.h): the learning-rate schedule and the decoupled weight decay of hgn_adam_step_sched."""
+    _fields_ = [('lr', C.c_float), ('lr_min', C.c_float), ('warmup_steps', C.c_int32), ('decay_steps', C.c_int32),
+                ('decay_rate', C.c_float), ('weight_decay', C.c_float)]
+
+
 _SIGS = {
     'hgn_last_error': (C.c_char_p, []),
     'hgn_version': (C.c_int, []),
@@ -165,6 +171,9 @@ _SIGS = {
                                      C.c_size_t, C.c_void_p]),
     'hgn_adam_step_clip': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    'hgn_lr_at': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
+    'hgn_adam_step_sched': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/hgn_features.h
     'hgn_cells_to_edges_workspace_bytes': (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
     'hgn_cells_to_edges': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),

@@ -1591,6 +1591,38 @@ def adam_step_clip(p, g, m, v, lr, b1, b2, eps, step_dev, coef, grad_scale=1.0):
                                              step_dev.data_ptr(), grad_scale, coef.data_ptr(), _lib.stream_ptr()), 'hgn_adam_step_clip')
 
 
+def adam_step_sched(p, g, m, v, sched, b1, b2, eps, step_dev, *, count_step, grad_scale=1.0, coef=None, decay_mask=None, lr_out=None):
+    """Adam with the learning rate of the step formed on the device from ``step_dev`` under ``sched`` (a `_lib.AdamSched`:
+    `parallel.LRSchedule.as_struct(weight_decay)`) and AdamW's decoupled weight decay (include/hgn_mp.h: hgn_adam_step_sched; no
+    host read: a captured step replays a rate that moves).  ``count_step``: increment ``step_dev`` first (`adam_step_dev`), or read
+    it as it is (`adam_step_clip` behind `grad_norm_clip`).  ``coef``: one fp32 device element, the gradient is multiplied by
+    grad_scale * coef[0], and a coefficient of exactly 0 leaves p, m, v and lr_out untouched.  ``decay_mask``: uint8 [n], the
+    elements that decay (None: all of them).  ``lr_out``: one fp32 device element that receives the rate of this step."""
+    what = 'adam_step_sched'
+    _check_flat(what, p, g, m, v)
+    n = p.numel()
+    if not (n == g.numel() == m.numel() == v.numel()) or any(t.device != p.device for t in (g, m, v)):
+        raise _lib.HgnError('adam_step_sched: p, g, m, v must have one size and device')
+    for name, t in (('coef', coef), ('lr_out', lr_out)):
+        if t is not None:
+            _check_flat(what, t)
+            if t.numel() != 1 or t.device != p.device:
+                raise _lib.HgnError(f'adam_step_sched: {name} must be one fp32 element on the parameters\' device')
+    if step_dev is None:
+        raise _lib.HgnError('adam_step_sched: step_dev is required')
+    _check_counter(what, 'step_dev', step_dev, p.device)
+    if decay_mask is not None:
+        _lib.require_gpu(decay_mask)
+        if decay_mask.dtype != torch.uint8 or not decay_mask.is_contiguous() or decay_mask.numel() != n or decay_mask.device != p.device:
+            raise _lib.HgnError('adam_step_sched: decay_mask must be a contiguous uint8 tensor of n elements on the parameters\' device')
+    if not isinstance(sched, _lib.AdamSched):
+        raise _lib.HgnError('adam_step_sched: sched must be a _lib.AdamSched (parallel.LRSchedule.as_struct)')
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.check(_lib.lib().hgn_adam_step_sched(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, C.byref(sched), b1, b2, eps,
+                                              step_dev.data_ptr(), 1 if count_step else 0, grad_scale, ptr(coef), ptr(decay_mask),
+                                              ptr(lr_out), _lib.stream_ptr()), 'hgn_adam_step_sched')
+
+
 def prof_enable(on: bool):
     _lib.check(_lib.lib().hgn_prof_enable(1 if on else 0))
 

@@ -89,9 +89,100 @@ class FlatParams:
                 p.grad = self.grad[off:off + n].view(p.shape)
 
 
-def _torch_adam(p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0):
-    """Reference-semantics Adam on flat tensors (used only where the HIP kernel cannot run: CPU gloo tests)."""
+class LRSchedule:
+    """Learning rate of Adam's step t = 1, 2, ... : a linear warm-up over ``warmup_steps`` steps times an exponential decay from
+    ``lr`` towards the floor ``lr_min``, by ``decay_rate`` per ``decay_steps`` steps counted from the end of the warm-up (the
+    MeshGraphNets recipe: lr 1e-4 + 1e-6, lr_min 1e-6, decay_rate 0.1, decay_steps 5e6):
+
+        lr(t) = w(t) * (lr_min + (lr - lr_min) * decay_rate ** (max(0, t - warmup_steps) / decay_steps)),
+        w(t) = min(1, t / warmup_steps) for warmup_steps > 0, else 1;  decay_steps == 0: no decay, the bracket is lr.
+
+    An immutable value (it pickles, compares and hashes by its fields).  `at` is that formula in Python doubles on the fields as
+    given; the C ABI (`as_struct` -> hgn_adam_sched_t, what the device kernel evaluates) holds lr, lr_min and decay_rate as
+    float, so host and device agree to the last bits of pow for fields that are float32 numbers (`as_float32` rounds them) and
+    to 2^-24 relative per field otherwise.  The constructor refuses what the ABI refuses, with ValueError."""
+    __slots__ = ('lr', 'warmup_steps', 'decay_steps', 'decay_rate', 'lr_min')
+
+    def __init__(self, lr, warmup_steps=0, decay_steps=0, decay_rate=1.0, lr_min=0.0):
+        import math
+        lr, decay_rate, lr_min = float(lr), float(decay_rate), float(lr_min)
+        for name, n in (('warmup_steps', warmup_steps), ('decay_steps', decay_steps)):
+            if isinstance(n, bool) or int(n) != n or not 0 <= int(n) < 2 ** 31:
+                raise ValueError(f'LRSchedule: {name} must be an integer in [0, 2^31), got {n!r}')
+        if not math.isfinite(lr) or lr < 0:
+            raise ValueError(f'LRSchedule: lr must be finite and >= 0, got {lr!r}')
+        if not 0.0 <= lr_min <= lr:
+            raise ValueError(f'LRSchedule: lr_min must lie in [0, lr], got {lr_min!r}')
+        if not 0.0 < decay_rate <= 1.0:
+            raise ValueError(f'LRSchedule: decay_rate must lie in (0, 1], got {decay_rate!r}')
+        for name, val in (('lr', lr), ('warmup_steps', int(warmup_steps)), ('decay_steps', int(decay_steps)),
+                          ('decay_rate', decay_rate), ('lr_min', lr_min)):
+            object.__setattr__(self, name, val)
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError('LRSchedule is immutable')
+
+    __delattr__ = __setattr__
+
+    def fields(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __reduce__(self):
+        return (LRSchedule, tuple(getattr(self, k) for k in self.__slots__))
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.fields() == other.fields()
+
+    def __hash__(self):
+        return hash(tuple(self.fields().items()))
+
+    def __repr__(self):
+        return 'LRSchedule(%s)' % ', '.join(f'{k}={v!r}' for k, v in self.fields().items())
+
+    def at(self, t: int) -> float:
+        """The rate of step t >= 1 (hgn_lr_at's formula, operation for operation)."""
+        if int(t) != t or t < 1:
+            raise ValueError(f'LRSchedule.at: steps count from 1, got {t!r}')
+        t = int(t)
+        rate = self.lr
+        if self.decay_steps > 0:
+            rate = self.lr_min + (self.lr - self.lr_min) * self.decay_rate ** (float(max(0, t - self.warmup_steps)) / float(self.decay_steps))
+        if self.warmup_steps > 0 and t < self.warmup_steps:
+            rate = (float(t) / float(self.warmup_steps)) * rate
+        return rate
+
+    def as_float32(self) -> 'LRSchedule':
+        """The schedule the device evaluates: lr, lr_min and decay_rate rounded to float32."""
+        f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
+        lr = f32(self.lr)
+        return LRSchedule(lr, self.warmup_steps, self.decay_steps, min(1.0, f32(self.decay_rate)), min(lr, f32(self.lr_min)))
+
+    def as_struct(self, weight_decay: float = 0.0):
+        """-> _lib.AdamSched (hgn_adam_sched_t) with this schedule and ``weight_decay``."""
+        from . import _lib
+        _check_weight_decay(self.lr, weight_decay)
+        return _lib.AdamSched(self.lr, self.lr_min, self.warmup_steps, self.decay_steps, self.decay_rate, float(weight_decay))
+
+
+def _check_weight_decay(lr, weight_decay):
+    import math
+    wd = float(weight_decay)
+    if not math.isfinite(wd) or wd < 0:
+        raise ValueError(f'weight_decay must be finite and >= 0, got {weight_decay!r}')
+    if lr * wd >= 1.0:
+        raise ValueError(f'lr * weight_decay must be < 1, got {lr!r} * {wd!r}')
+
+
+def _torch_adam(p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0, weight_decay=0.0, decay_mask=None):
+    """Reference-semantics Adam on flat tensors (used only where the HIP kernel cannot run: CPU gloo tests).  ``weight_decay``:
+    torch.optim.AdamW's decoupled decay, p *= 1 - lr * weight_decay before the update, where ``decay_mask`` (None: everywhere)
+    is not zero."""
     g = g * grad_scale
+    if weight_decay > 0:
+        if decay_mask is None:
+            p.mul_(1 - lr * weight_decay)
+        else:
+            p.mul_(torch.where(decay_mask != 0, 1 - lr * weight_decay, 1.0).to(p.dtype))
     m.mul_(b1).add_(g, alpha=1 - b1)
     v.mul_(b2).addcmul_(g, g, value=1 - b2)
     bc1 = 1 - b1 ** step
@@ -185,12 +276,27 @@ class DataParallelTrainer:
     number of skipped steps) are device tensors the trainer never reads: a caller logs them when it wants.  With both unset the
     step is launch for launch what it is without them.  On the device the clipped update is the library's own kernel, as with
     ``device_step``; an ``adam_fn`` is called for CPU tensors only (with the coefficient as its ``grad_scale``), and
-    ``skip_nonfinite`` refuses any but `_torch_adam`."""
+    ``skip_nonfinite`` refuses any but `_torch_adam`.
+
+    ``lr_schedule`` (an `LRSchedule`) and ``weight_decay`` (decoupled, torch.optim.AdamW's: p *= 1 - lr_t * weight_decay before
+    the update, with the step's rate): the rate of a step is formed ON THE DEVICE from the step counter
+    (ops.adam_step_sched in place of ops.adam_step_dev / ops.adam_step_clip), so a captured step replays a rate that moves.
+    Either one puts the step counter on the device and creates `lr_dev`, one fp32 device element with the rate of the last
+    counted step, which the trainer never reads.  ``weight_decay`` alone means the constant schedule at ``lr``.
+    ``decay_filter(name, param) -> bool`` selects the tensors that decay; the default takes those with ``dim() >= 2`` (weights,
+    not biases or LayerNorm vectors).  `decay_mask` is the uint8 mask over the flat buffer, built once, None when every tensor
+    decays.  A skipped step decays nothing.  With both unset the step is launch for launch what it is without them.  CPU
+    tensors take the same arithmetic in torch, with lr = schedule.at(step); ``weight_decay`` refuses an ``adam_fn`` other than
+    `_torch_adam`.
+
+    `state_dict()` / `load_state_dict()` carry the optimiser's side of a run -- m, v, the counters, the hyper-parameters, the
+    layout of the flat buffer -- so that a run resumed from the model's and the trainer's state continues bit for bit."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  group: Optional[dist.ProcessGroup] = None, adam_fn: Optional[Callable] = None,
                  device_step: bool = False, wgrad_stream: bool = False, buckets: int = 4, bucket_after=None,
-                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 lr_schedule: Optional[LRSchedule] = None, weight_decay: float = 0.0, decay_filter: Optional[Callable] = None):
         self.model = model
         from . import ops as _ops
         self.ctx = getattr(model, '_hgn_ctx', None) or _ops.default_context()      # the launch context of the model it trains (ops.Context)
@@ -221,6 +327,25 @@ class DataParallelTrainer:
                 self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
             self.grad_stats = torch.zeros(2, dtype=torch.float32, device=dev)      # [norm, coef] of the last step; never read here
             self.skipped_dev = torch.zeros(1, dtype=torch.int32, device=dev)       # steps skipped as non-finite
+        # learning-rate schedule / decoupled weight decay: the rate is formed on the device from the step counter (class docstring)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError('lr_schedule must be a parallel.LRSchedule')
+        self.weight_decay = float(weight_decay)
+        self.lr_schedule = lr_schedule
+        self.sched = lr_schedule if lr_schedule is not None else (LRSchedule(lr) if self.weight_decay != 0 else None)
+        _check_weight_decay(self.sched.lr if self.sched is not None else lr, weight_decay)
+        if self.weight_decay > 0 and adam_fn is not None and adam_fn is not _torch_adam:
+            raise ValueError('weight_decay needs the trainer\'s own update (the decay is part of it): no adam_fn other than '
+                             'parallel._torch_adam')
+        self.lr_dev = self.decay_mask = self._sched_struct = None
+        if self.sched is not None:
+            dev = self.fp.flat.device
+            if self.t_dev is None:                                   # the rate follows the device's step count
+                self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)          # rate of the last counted step; never read here
+            self._sched_struct = self.sched.as_struct(self.weight_decay)
+            if self.weight_decay > 0:
+                self.decay_mask = self._build_decay_mask(decay_filter)
         if adam_fn is None:
             from . import ops
             adam_fn = ops.adam_step
@@ -229,6 +354,21 @@ class DataParallelTrainer:
         self.overlap = True                                        # False: every range after the backward pass (graphs.GraphedShardStep)
         self._pending, self._done_upto = [], None
         self.bucket_starts = self._plan_buckets(max(1, int(buckets)), bucket_after) if self.collectives else []
+
+    def _build_decay_mask(self, decay_filter):
+        """uint8 over the flat buffer: 1 on the elements of the tensors ``decay_filter(name, param)`` selects (default: dim() >= 2);
+        None when it selects every tensor (the padding between tensors holds zeros, which decay to zeros)."""
+        if decay_filter is None:
+            decay_filter = lambda name, param: param.dim() >= 2
+        name_of = {id(p): n for n, p in self.model.named_parameters()}
+        chosen = [bool(decay_filter(name_of[id(p)], p)) for p in self.fp.params]
+        if all(chosen):
+            return None
+        mask = torch.zeros(self.fp.numel, dtype=torch.uint8)
+        for p, off, yes in zip(self.fp.params, self.fp.offsets, chosen):
+            if yes:
+                mask[off:off + p.numel()] = 1
+        return mask.to(self.fp.flat.device)
 
     # ---- bucket plan ------------------------------------------------------------------------------------------------
     def _plan_buckets(self, n_buckets: int, bucket_after):
@@ -375,6 +515,8 @@ class DataParallelTrainer:
         self.t += 1
         if self.clip:
             self._clipped_update()
+        elif self.sched is not None:
+            self._scheduled_update()
         elif self.t_dev is not None:
             from . import ops
             ops.adam_step_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t_dev)
@@ -394,7 +536,11 @@ class DataParallelTrainer:
             from . import ops
             with ops.using(self.ctx):
                 ops.grad_norm_clip(fp.grad, self.max_grad_norm, self.grad_stats, self.t_dev, self.skipped_dev, self.skip_nonfinite)
-            ops.adam_step_clip(fp.flat, fp.grad, self.m, self.v, self.lr, b1, b2, self.eps, self.t_dev, self.grad_stats[1:2])
+            if self.sched is not None:
+                ops.adam_step_sched(fp.flat, fp.grad, self.m, self.v, self._sched_struct, b1, b2, self.eps, self.t_dev, count_step=False,
+                                    coef=self.grad_stats[1:2], decay_mask=self.decay_mask, lr_out=self.lr_dev)
+            else:
+                ops.adam_step_clip(fp.flat, fp.grad, self.m, self.v, self.lr, b1, b2, self.eps, self.t_dev, self.grad_stats[1:2])
             return
         total = fp.grad.double().square().sum()
         norm = total.sqrt()
@@ -409,7 +555,89 @@ class DataParallelTrainer:
             self.t_dev += 1
         self.grad_stats[0], self.grad_stats[1] = norm.to(torch.float32), coef
         if coef != 0.0:
-            self.adam_fn(fp.flat, fp.grad, self.m, self.v, self.lr, b1, b2, self.eps, int(self.t_dev), grad_scale=coef)
+            self.adam_fn(fp.flat, fp.grad, self.m, self.v, self._host_rate(), b1, b2, self.eps, int(self.t_dev), grad_scale=coef,
+                         **self._decay_keywords())
+
+    def _host_rate(self) -> float:
+        """CPU tensors: the rate of the step `t_dev` has just counted (and `lr_dev`), or the constant one."""
+        if self.sched is None:
+            return self.lr
+        lr = self.sched.at(int(self.t_dev))
+        self.lr_dev.fill_(lr)
+        return lr
+
+    def _decay_keywords(self):
+        return dict(weight_decay=self.weight_decay, decay_mask=self.decay_mask) if self.weight_decay > 0 else {}
+
+    def _scheduled_update(self):
+        """Adam at the schedule's rate with decoupled weight decay, no clipping: one ops.adam_step_sched, which counts the step and
+        forms the rate from the count on the device; CPU tensors: the same in torch at lr = schedule.at(step)."""
+        fp, (b1, b2) = self.fp, self.betas
+        if fp.flat.is_cuda:
+            from . import ops
+            ops.adam_step_sched(fp.flat, fp.grad, self.m, self.v, self._sched_struct, b1, b2, self.eps, self.t_dev, count_step=True,
+                                decay_mask=self.decay_mask, lr_out=self.lr_dev)
+            return
+        self.t_dev += 1
+        self.adam_fn(fp.flat, fp.grad, self.m, self.v, self._host_rate(), b1, b2, self.eps, int(self.t_dev), **self._decay_keywords())
+
+    # ---- resume -----------------------------------------------------------------------------------------------------
+    _STATE_TENSORS = ('m', 'v', 't_dev', 'skipped_dev', 'grad_stats', 'lr_dev')
+
+    def _hyper_parameters(self):
+        sched = self.lr_schedule.fields() if self.lr_schedule is not None else None
+        return {'lr': float(self.lr), 'betas': [float(b) for b in self.betas], 'eps': float(self.eps), 'lr_schedule': sched,
+                'weight_decay': self.weight_decay, 'max_grad_norm': self.max_grad_norm, 'skip_nonfinite': self.skip_nonfinite}
+
+    def _layout(self):
+        name_of = {id(p): n for n, p in self.model.named_parameters()}
+        return {'names': [name_of[id(p)] for p in self.fp.params], 'offsets': [int(o) for o in self.fp.offsets],
+                'sizes': [int(p.numel()) for p in self.fp.params], 'numel': int(self.fp.numel)}
+
+    def state_dict(self):
+        """The optimiser's side of the run as CPU tensors and plain values (torch.save / torch.load(weights_only=True)): m, v, the
+        host step count `t`, the device tensors that exist (t_dev, skipped_dev, grad_stats, lr_dev), the hyper-parameters and the
+        layout of the flat buffer (parameter names, offsets, sizes).  The parameters travel in the model's state_dict."""
+        state = {'t': int(self.t), 'hyper_parameters': self._hyper_parameters(), 'layout': self._layout()}
+        for k in self._STATE_TENSORS:
+            x = getattr(self, k)
+            if x is not None:
+                state[k] = x.detach().cpu().clone()
+        return state
+
+    def load_state_dict(self, state):
+        """Take over m, v and the counters of `state_dict()`'s result, IN PLACE (captured graphs hold the tensors' addresses).  A
+        flat-buffer layout that differs from this trainer's raises ValueError naming the first difference; hyper-parameters that
+        differ are reported with a warning and this trainer's own stay in force.  The parameters are not touched: load the model's
+        state_dict (before or after)."""
+        mine, theirs = self._layout(), state['layout']
+        for i, (a, b) in enumerate(zip(zip(mine['names'], mine['offsets'], mine['sizes']),
+                                       zip(theirs['names'], theirs['offsets'], theirs['sizes']))):
+            if a != b:
+                raise ValueError('load_state_dict: the flat buffer is laid out differently: parameter %d is %s at offset %d with %d '
+                                 'elements here, %s at offset %d with %d elements in the state' % ((i,) + a + b))
+        if len(mine['names']) != len(theirs['names']) or mine['numel'] != theirs['numel']:
+            raise ValueError('load_state_dict: the flat buffer is laid out differently: %d parameters in %d elements here, %d in %d '
+                             'in the state' % (len(mine['names']), mine['numel'], len(theirs['names']), theirs['numel']))
+        have, saved = self._hyper_parameters(), state.get('hyper_parameters', {})
+        differ = [f'{k}: {have[k]!r} here, {saved.get(k)!r} in the state' for k in have if saved.get(k) != have[k]]
+        if differ:
+            import warnings
+            warnings.warn('load_state_dict: hyper-parameters differ, this trainer\'s own stay in force -- ' + '; '.join(differ))
+        for k in ('m', 'v'):
+            if tuple(state[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError(f'load_state_dict: {k} has {tuple(state[k].shape)} elements, the flat buffer {tuple(self.m.shape)}')
+        for k in self._STATE_TENSORS:
+            x = getattr(self, k)
+            if x is None:
+                continue
+            if k in state:
+                x.copy_(state[k])
+            elif k == 't_dev':                                       # saved by a trainer that counted on the host
+                x.fill_(int(state['t']))
+        self.t = int(state['t'])
+        if self.fp.flat.is_cuda:
+            self.ctx.invalidate_packs()
 
 
 def attach_normalizer_sync(normalizers: Iterable, group: Optional[dist.ProcessGroup] = None):

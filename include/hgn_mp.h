@@ -437,6 +437,39 @@ int hgn_grad_clip_coef(const float* g, int64_t n, float max_norm, int skip_nonfi
                        int32_t* skipped_dev, void* ws, size_t ws_bytes, void* stream);
 int hgn_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, const int32_t* step_dev, float grad_scale, const float* coef_dev, void* stream);
+/* Learning-rate schedule and decoupled weight decay (torch.optim.AdamW) as device-side parts of the step: the rate of a captured
+ * step is not the float it was captured with, it follows *step_dev like the bias corrections do.  With t the 1-based step count
+ * Adam uses, in double:
+ *   lr(t) = w(t) * (lr_min + (lr - lr_min) * decay_rate^(max(0, t - warmup_steps) / decay_steps)),
+ *   w(t) = min(1, t / warmup_steps) for warmup_steps > 0, else 1;  decay_steps == 0: the power is 1 and the bracket is lr.
+ * hgn_lr_at evaluates it on the host (no GPU needed); the kernel of hgn_adam_step_sched compiles the same inline function.
+ * hgn_adam_step_sched: count_step != 0 increments *step_dev first (hgn_adam_step_dev), count_step == 0 reads it as it is
+ * (hgn_adam_step_clip behind hgn_grad_clip_coef).  coef_dev non-null: every gradient entry is multiplied by
+ * (grad_scale * *coef_dev), the product formed first in fp32, and a coefficient of exactly 0 stores nothing -- not p, m, v, not
+ * lr_out: a skipped step decays nothing.  Element i: m, v as hgn_adam_step_dev, then
+ *   p <- p * (1 - lr_t * weight_decay) - (lr_t / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),
+ * the first factor (formed in double, applied as one fp32 product) only where weight_decay > 0 and (decay_mask == NULL or
+ * decay_mask[i] != 0).  lr_out non-null: (float) lr_t is stored there (n > 0).  Thread 0 of every workgroup forms the bias
+ * corrections and lr_t from *step_dev in double (under the latency of the workgroup's loads, which are issued first); nothing is
+ * reduced, no atomics: replicas of a data-parallel run stay bit-equal.
+ * With warmup_steps = decay_steps = 0 and weight_decay = 0 the results are bit for bit those of hgn_adam_step_dev (count_step,
+ * no coef_dev) and of hgn_adam_step_clip (no count_step, coef_dev).  Refused (HGN_E_INVALID, before any launch): a null
+ * p / g / m / v with n > 0, null s / step_dev, n < 0, lr negative or not finite, lr_min outside [0, lr], negative step counts,
+ * decay_rate outside (0, 1], weight_decay negative or not finite, lr * weight_decay >= 1.  n == 0 launches nothing but the
+ * counter increment.  hgn_lr_at also refuses step < 1. */
+typedef struct hgn_adam_sched_t {
+  float   lr;            /* base rate */
+  float   lr_min;        /* floor the decay approaches, 0 <= lr_min <= lr */
+  int32_t warmup_steps;  /* 0: none */
+  int32_t decay_steps;   /* 0: constant after the warm-up */
+  float   decay_rate;    /* in (0, 1] */
+  float   weight_decay;  /* decoupled (AdamW), >= 0 */
+} hgn_adam_sched_t;
+int hgn_lr_at(const hgn_adam_sched_t* s, int32_t step, double* lr);
+int hgn_adam_step_sched(float* p, const float* g, float* m, float* v, int64_t n, const hgn_adam_sched_t* s, float beta1,
+                        float beta2, float eps, int32_t* step_dev, int count_step, float grad_scale,
+                        const float* coef_dev /*nullable*/, const uint8_t* decay_mask /*nullable*/, float* lr_out /*nullable*/,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line).
