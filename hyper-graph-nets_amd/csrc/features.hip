@@ -318,6 +318,140 @@ __global__ void training_noise_kernel(const float* __restrict__ x, long ldx, int
   }
 }
 
+// Per-frame masked mean squared errors (flag.py:150-167, cylinder.py:123-153, plate.py:218-244; MeshSimulator.py:151-156,295-297).
+// A frame is cut into chunks of HGN_LOSS_CHUNK_ROWS rows counted from ITS OWN first row; one workgroup per chunk, one thread per row.
+// A thread adds the squares of its row in ascending column order; partials are doubles and meet lanes -> waves -> (finalise) chunks of
+// a frame in ascending order -> frames in ascending order for the entry over all rows.  No atomics: equal bits on every run, and what
+// a frame gets depends on its own rows alone.  The statistics of a column are formed once per workgroup with the expressions of
+// rollout_advance_kernel (same operations on the same values: same bits), and v is that kernel's v.
+static_assert(HGN_LOSS_CHUNK_ROWS == 256, "one thread per row of a chunk, four wavefronts per workgroup");
+__device__ __forceinline__ double loss_block_sum(double s, double* lds) {
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);    // (every thread: only thread 0's copy is used)
+}
+
+__global__ __launch_bounds__(HGN_LOSS_CHUNK_ROWS) void frame_losses_partial_kernel(
+    const float* __restrict__ net_out, long ld_out, const float* __restrict__ target, long ld_tgt, int F,
+    const int64_t* __restrict__ node_type, long ldt, unsigned free_mask, long rows_per_frame, long chunks_per_frame,
+    const float* __restrict__ acc_sum, const float* __restrict__ acc_sumsq, const float* __restrict__ acc_count, float eps,
+    const float* __restrict__ cur, long ld_cur, int d, float ca, const float* __restrict__ prev, long ld_prev, float cp,
+    const float* __restrict__ state_target, long ld_st, double* __restrict__ part_s, double* __restrict__ part_e,
+    long long* __restrict__ part_n) {
+  __shared__ float mean[HGN_MAX_FEATURE_WIDTH], sd[HGN_MAX_FEATURE_WIDTH];
+  __shared__ double lds_s[HGN_LOSS_CHUNK_ROWS / 64], lds_e[HGN_LOSS_CHUNK_ROWS / 64];
+  __shared__ int lds_n[HGN_LOSS_CHUNK_ROWS / 64];
+  const int t = threadIdx.x;
+  if (cur && t < d) {
+    const float safe = fmaxf(*acc_count, 1.f);
+    const float m = acc_sum[t] / safe;
+    mean[t] = m;
+    sd[t] = fmaxf(sqrtf(fabsf(acc_sumsq[t] / safe - m * m)), eps);
+  }
+  __syncthreads();
+  const long f = (long)blockIdx.x / chunks_per_frame;
+  const long k = (long)blockIdx.x - f * chunks_per_frame;
+  const long local = k * HGN_LOSS_CHUNK_ROWS + t;               // the row's place in its frame
+  bool is_free = false;
+  double s = 0.0, e = 0.0;
+  if (local < rows_per_frame) {
+    const long r = f * rows_per_frame + local;
+    const int64_t ty = node_type[r * ldt];
+    is_free = ty >= 0 && ty < 32 && ((free_mask >> (unsigned)ty) & 1u);
+    if (is_free) {
+      const float* o = net_out + r * ld_out;
+      const float* g = target + r * ld_tgt;
+      for (int c = 0; c < F; ++c) {
+        const double diff = (double)o[c] - (double)g[c];
+        s += diff * diff;
+      }
+      if (cur) {
+        for (int c = 0; c < d; ++c) {
+          const float x = o[c] * sd[c] + mean[c];                // Normalizer.inverse
+          float v = ca * cur[r * ld_cur + c] + 1.f * x;          // lincomb3 with cb = 1
+          if (prev) v = v + cp * prev[r * ld_prev + c];
+          const double diff = (double)v - (double)state_target[r * ld_st + c];
+          e += diff * diff;
+        }
+      }
+    }
+  }
+  const int n_wave = __popcll(__ballot(is_free));
+  if ((t & 63) == 0) lds_n[t >> 6] = n_wave;
+  const double S = loss_block_sum(s, lds_s);                     // its barrier also covers lds_n
+  const double E = loss_block_sum(e, lds_e);
+  if (t == 0) {
+    part_s[blockIdx.x] = S;
+    part_e[blockIdx.x] = E;
+    part_n[blockIdx.x] = (long long)((lds_n[0] + lds_n[1]) + (lds_n[2] + lds_n[3]));
+  }
+}
+
+// One workgroup.  Frames are taken 256 at a time: thread t adds the chunks of frame base + t in ascending order and writes the frame's
+// entries; the three running totals are then advanced over these 256 frames in ascending order by one thread each.
+__global__ __launch_bounds__(256) void frame_losses_final_kernel(const double* __restrict__ part_s, const double* __restrict__ part_e,
+                                                                 const long long* __restrict__ part_n, long n_frames,
+                                                                 long chunks_per_frame, int F, int d, float* __restrict__ loss,
+                                                                 float* __restrict__ state_err, int64_t* __restrict__ count) {
+  __shared__ double fs[256], fe[256];
+  __shared__ long long fn[256];
+  __shared__ double tot_s, tot_e;
+  __shared__ long long tot_n;
+  const int t = threadIdx.x;
+  if (t == 0) { tot_s = 0.0; tot_e = 0.0; tot_n = 0; }
+  for (long base = 0; base < n_frames; base += 256) {
+    const long f = base + t;
+    double S = 0.0, E = 0.0;
+    long long n = 0;
+    if (f < n_frames) {
+      for (long k = 0; k < chunks_per_frame; ++k) {
+        const long b = f * chunks_per_frame + k;
+        S += part_s[b]; E += part_e[b]; n += part_n[b];
+      }
+      loss[f] = (float)(S / ((double)n * (double)F));              // n = 0: IEEE 0 / 0 = NaN
+      if (state_err) state_err[f] = (float)(E / ((double)n * (double)d));
+      count[f] = (int64_t)n;
+    }
+    fs[t] = S; fe[t] = E; fn[t] = n;
+    __syncthreads();
+    const int live = (int)(n_frames - base < 256 ? n_frames - base : 256);
+    if (t == 0) { double a = tot_s; for (int j = 0; j < live; ++j) a += fs[j]; tot_s = a; }
+    if (t == 64) { double a = tot_e; for (int j = 0; j < live; ++j) a += fe[j]; tot_e = a; }
+    if (t == 128) { long long a = tot_n; for (int j = 0; j < live; ++j) a += fn[j]; tot_n = a; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    loss[n_frames] = (float)(tot_s / ((double)tot_n * (double)F));
+    if (state_err) state_err[n_frames] = (float)(tot_e / ((double)tot_n * (double)d));
+    count[n_frames] = (int64_t)tot_n;
+  }
+}
+
+// Backward of the losses with respect to the network output and the target, flat over [rows, F]: a free row of frame f gets
+// (2 (net - target)) * w with w = g[f] / (n_f F) + g[B] / (n_all F) formed in double and rounded once; every other row gets zeros.
+// Every element of every output given is written exactly once.  No LDS, no atomics.
+__global__ void frame_losses_bwd_kernel(const float* __restrict__ net_out, long ld_out, const float* __restrict__ target, long ld_tgt,
+                                        int F, const int64_t* __restrict__ node_type, long ldt, unsigned free_mask, long rows,
+                                        long rows_per_frame, const int64_t* __restrict__ count, const float* __restrict__ g,
+                                        float* __restrict__ d_net, long ld_dn, float* __restrict__ d_target, long ld_dt) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * F) return;
+  const long r = i / F;
+  const int c = (int)(i - r * F);
+  const int64_t ty = node_type[r * ldt];
+  const bool is_free = ty >= 0 && ty < 32 && ((free_mask >> (unsigned)ty) & 1u);
+  float v = 0.f;
+  if (is_free && g) {
+    const long f = r / rows_per_frame, B = rows / rows_per_frame;
+    const float w = (float)((double)g[f] / ((double)count[f] * (double)F) + (double)g[B] / ((double)count[B] * (double)F));
+    const float diff = net_out[r * ld_out + c] - target[r * ld_tgt + c];
+    v = (2.f * diff) * w;
+  }
+  if (d_net) d_net[r * ld_dn + c] = v;
+  if (d_target) d_target[r * ld_dt + c] = -v;
+}
+
 // Backward of the cluster mean of the connector (hierarchical_connector.py:39-45; rmp.py: `means_all = ...` in
 // HierarchicalConnector.run) with respect to the node rows.  Node-parallel, flat over [rows, D]: thread (n, c) walks row n's own
 // memberships q in [node_rowptr[n], node_rowptr[n+1]) in that order -- j = node_items[q] is a position of the member list, s =
@@ -915,6 +1049,81 @@ extern "C" int hgn_training_noise(const float* x, int64_t ldx, int d, const int6
                      (unsigned)(seed >> 32), (unsigned)(draw & 0xffffffffu), (unsigned)(draw >> 32), std_, target, (long)ld_tgt,
                      target_scale, out_x, (long)ld_ox, out_target, (long)ld_ot);
   return hgn_check_launch("hgn_training_noise");
+}
+
+// -> the number of chunks (= workgroups of the partial pass) of rows / rows_per_frame frames, or -1 for sizes the entries refuse
+static int64_t loss_chunks(int64_t rows, int64_t rows_per_frame, int64_t* chunks_per_frame) {
+  if (rows < 0 || rows > 0x7fffffff || rows_per_frame < 1 || rows % rows_per_frame != 0) return -1;
+  *chunks_per_frame = (rows_per_frame + HGN_LOSS_CHUNK_ROWS - 1) / HGN_LOSS_CHUNK_ROWS;
+  return (rows / rows_per_frame) * *chunks_per_frame;
+}
+
+extern "C" int hgn_frame_losses_workspace_bytes(int64_t rows, int64_t rows_per_frame, size_t* bytes) {
+  int64_t cpf = 0;
+  const int64_t chunks = loss_chunks(rows, rows_per_frame, &cpf);
+  if (!bytes || chunks < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_workspace_bytes: bad sizes (0 <= rows < 2^31, rows_per_frame >= 1 and divides rows)");
+  *bytes = (size_t)chunks * 3 * sizeof(double);
+  return HGN_OK;
+}
+
+extern "C" int hgn_frame_losses(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                                const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows, int64_t rows_per_frame,
+                                const float* acc_sum, const float* acc_sumsq, const float* acc_count, float eps, const float* cur,
+                                int64_t ld_cur, int d, float ca, const float* prev, int64_t ld_prev, float cp,
+                                const float* state_target, int64_t ld_st, float* loss, float* state_err, int64_t* count,
+                                void* workspace, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t cpf = 0;
+  const int64_t chunks = loss_chunks(rows, rows_per_frame, &cpf);
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || chunks < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: bad sizes (1 <= F <= 32, 0 <= rows < 2^31, rows_per_frame >= 1 and divides rows)");
+  const int given = (acc_sum != nullptr) + (acc_sumsq != nullptr) + (acc_count != nullptr) + (cur != nullptr) + (state_target != nullptr);
+  if ((given != 0 && given != 5) || (given == 0 && prev))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: the state part (statistics, cur, state_target; prev optional) must be given whole or not at all");
+  const bool with_state = given == 5;
+  if (with_state != (state_err != nullptr))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: state_err must be given exactly when the state part is");
+  if (with_state && (d < 1 || d > F)) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: bad state width (1 <= d <= F)");
+  if (ld_out < F || ld_tgt < F || ldt < 1 || (with_state && (ld_cur < d || ld_st < d || (prev && ld_prev < d))))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (rows == 0) return HGN_OK;
+  if (!net_out || !target || !node_type || !loss || !count) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: null pointer");
+  if (!workspace || ((uintptr_t)workspace & 7)) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: null or misaligned workspace");
+  if (ws_bytes < (size_t)chunks * 3 * sizeof(double))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses: workspace too small (hgn_frame_losses_workspace_bytes)");
+  ProfScope ps(13, (double)rows, stream);
+  double* part_s = (double*)workspace;
+  double* part_e = part_s + chunks;
+  long long* part_n = (long long*)(part_e + chunks);
+  hipLaunchKernelGGL(frame_losses_partial_kernel, dim3((unsigned)chunks), dim3(HGN_LOSS_CHUNK_ROWS), 0, stream, net_out, (long)ld_out,
+                     target, (long)ld_tgt, F, node_type, (long)ldt, (unsigned)free_mask, (long)rows_per_frame, (long)cpf, acc_sum,
+                     acc_sumsq, acc_count, eps, cur, (long)ld_cur, d, ca, prev, (long)ld_prev, cp, state_target, (long)ld_st, part_s,
+                     part_e, part_n);
+  hipLaunchKernelGGL(frame_losses_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)part_s, (const double*)part_e,
+                     (const long long*)part_n, (long)(rows / rows_per_frame), (long)cpf, F, with_state ? d : 1, loss, state_err, count);
+  return hgn_check_launch("hgn_frame_losses");
+}
+
+extern "C" int hgn_frame_losses_bwd(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                                    const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows, int64_t rows_per_frame,
+                                    const int64_t* count, const float* g, float* d_net, int64_t ld_dnet, float* d_target,
+                                    int64_t ld_dtgt, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t cpf = 0;
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || loss_chunks(rows, rows_per_frame, &cpf) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_bwd: bad sizes (1 <= F <= 32, 0 <= rows < 2^31, rows_per_frame >= 1 and divides rows)");
+  if (ld_out < F || ld_tgt < F || ldt < 1 || (d_net && ld_dnet < F) || (d_target && ld_dtgt < F))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_bwd: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (!d_net && !d_target) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_bwd: no output asked for (d_net and d_target are both null)");
+  if (rows == 0) return HGN_OK;
+  if (!net_out || !target || !node_type || !count) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_bwd: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  const int64_t n = rows * F;
+  hipLaunchKernelGGL(frame_losses_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, net_out, (long)ld_out, target,
+                     (long)ld_tgt, F, node_type, (long)ldt, (unsigned)free_mask, (long)rows, (long)rows_per_frame, count, g, d_net,
+                     (long)ld_dnet, d_target, (long)ld_dtgt);
+  return hgn_check_launch("hgn_frame_losses_bwd");
 }
 
 extern "C" int hgn_member_mean_bwd(const float* d_mean, int64_t ld_dmean, int D, const int32_t* seg_rowptr, int64_t S,

@@ -220,6 +220,14 @@ _SIGS = {
     'hgn_training_noise': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
                                      C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'hgn_frame_losses_workspace_bytes': (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    'hgn_frame_losses': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int64,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_float,
+                                   C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    'hgn_frame_losses_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32,
+                                       C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
     'hgn_member_mean_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_rel_edge_features_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,

@@ -2,6 +2,7 @@
 (SURVEY.md section 8 rows f2 / f3).  Device tensors in, device tensors out; nothing here falls back to torch math.
 """
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -43,6 +44,16 @@ def _type_column(node_type: torch.Tensor, dev, rows: int):
     if nt.dim() == 2:
         nt = nt[:, 0]
     return nt, (nt.stride(0) if rows > 1 else 1)
+
+
+def _free_mask(free_types, what: str) -> int:
+    """The node types whose rows are free as the bit mask the kernels take (the convention of hgn_rollout_advance)."""
+    free_mask = 0
+    for t in free_types:
+        if not 0 <= int(t) < 32:
+            raise ValueError(f'{what}: free node types must lie in [0, 32)')
+        free_mask |= 1 << int(t)
+    return free_mask
 
 
 def cells_to_edges(cells: torch.Tensor, deform: bool = False):
@@ -387,11 +398,7 @@ def rollout_advance(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int
     nt, ldt = _type_column(node_type, dev, rows)
     if nt.shape[0] != rows:
         raise ValueError(f'rollout_advance: {nt.shape[0]} node types for {rows} rows')
-    free_mask = 0
-    for t in free_types:
-        if not 0 <= int(t) < 32:
-            raise ValueError('rollout_advance: free node types must lie in [0, 32)')
-        free_mask |= 1 << int(t)
+    free_mask = _free_mask(free_types, 'rollout_advance')
     _out_rows(next_out, rows, d, 'next_out')
     if rec is not None:
         _out_rows(rec, rows, d, 'rec')
@@ -480,11 +487,7 @@ def _noise_into_fresh(x, node_type, free_types, std, seed, draw, target, target_
     nt, ldt = _type_column(node_type, dev, rows)
     if nt.shape[0] != rows:
         raise ValueError(f'add_noise: {nt.shape[0]} node types for {rows} rows')
-    free_mask = 0
-    for t in free_types:
-        if not 0 <= int(t) < 32:
-            raise ValueError('add_noise: free node types must lie in [0, 32)')
-        free_mask |= 1 << int(t)
+    free_mask = _free_mask(free_types, 'add_noise')
     per_frame = max(rows, 1) if rows_per_frame is None else int(rows_per_frame)
     if per_frame < 1 or rows % per_frame:
         raise ValueError(f'add_noise: {rows} rows do not split into frames of {rows_per_frame} rows')
@@ -542,6 +545,129 @@ def add_noise(x: torch.Tensor, node_type: torch.Tensor, free_types, std: float, 
     if _needs_grad(x, target):
         return _AddNoiseFn.apply(x, target, args)
     return _noise_into_fresh(x, *args[:5], target, *args[5:])
+
+
+class FrameLosses(NamedTuple):
+    """What frame_losses returns.  ``loss`` (0-d) is over all rows, ``per_frame`` [B] per frame; ``state_error`` / ``state_per_frame``
+    likewise for the updated state (None without a state part); ``count`` [B+1] int64: the free rows of every frame, then of all."""
+    loss: torch.Tensor
+    per_frame: torch.Tensor
+    state_error: Optional[torch.Tensor]
+    state_per_frame: Optional[torch.Tensor]
+    count: torch.Tensor
+
+
+def _frame_losses_launch(net_out, target, node_type, free_types, rows_per_frame, state):
+    """-> (loss [B+1], state_err [B+1] or None, count [B+1], what the backward launch needs)."""
+    dev = net_out.device
+    x = _f32_rows(net_out)
+    rows, F = x.shape
+    tgt = _f32_rows(target.to(dev))
+    if tgt.shape != x.shape:
+        raise ValueError(f'frame_losses: net_out {tuple(x.shape)} / target {tuple(tgt.shape)} shape mismatch')
+    nt, ldt = _type_column(node_type, dev, rows)
+    if nt.shape[0] != rows:
+        raise ValueError(f'frame_losses: {nt.shape[0]} node types for {rows} rows')
+    free_mask = _free_mask(free_types, 'frame_losses')
+    per_frame = max(rows, 1) if rows_per_frame is None else int(rows_per_frame)
+    if per_frame < 1 or rows % per_frame:
+        raise ValueError(f'frame_losses: {rows} rows do not split into frames of {rows_per_frame} rows')
+    B = rows // per_frame
+    nz = cur = prev = state_target = None
+    d, ca, cp, eps = 0, 0.0, 0.0, 0.0
+    if state is not None:
+        nz, cur, d, ca, prev, cp, state_target = state
+        d, eps = int(d), float(nz._eps)
+        if nz._acc_sum.numel() != F:
+            raise ValueError(f'frame_losses: the normaliser has {nz._acc_sum.numel()} columns, net_out {F}')
+        cur, state_target = _f32_rows(cur.to(dev)), _f32_rows(state_target.to(dev))
+        prev = _f32_rows(prev.to(dev)) if prev is not None else None
+        for name, t in (('cur', cur), ('prev', prev), ('state_target', state_target)):
+            if t is not None and tuple(t.shape) != (rows, d):
+                raise ValueError(f'frame_losses: {name} must be [{rows}, {d}]')
+    L = _lib.lib()
+    nb = C.c_size_t(0)
+    _lib.check(L.hgn_frame_losses_workspace_bytes(rows, per_frame, C.byref(nb)), 'hgn_frame_losses_workspace_bytes')
+    ws = torch.empty(max(nb.value // 8, 1), dtype=torch.float64, device=dev)        # a fresh buffer per call: capturable
+    loss = torch.empty(B + 1, dtype=torch.float32, device=dev)
+    state_err = torch.empty(B + 1, dtype=torch.float32, device=dev) if state is not None else None
+    count = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    _lib.check(L.hgn_frame_losses(
+        x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows, per_frame,
+        _ptr(nz._acc_sum) if nz is not None else None, _ptr(nz._acc_sum_squared) if nz is not None else None,
+        _ptr(nz._acc_count) if nz is not None else None, eps, _ptr(cur), _ld(cur), d, float(ca), _ptr(prev), _ld(prev), float(cp),
+        _ptr(state_target), _ld(state_target), loss.data_ptr(), _ptr(state_err), count.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+        _lib.stream_ptr()), 'hgn_frame_losses')
+    return loss, state_err, count, (x, tgt, nt, ldt, free_mask, per_frame)
+
+
+def _split_losses(loss, state_err, count) -> FrameLosses:
+    B = loss.shape[0] - 1
+    return FrameLosses(loss[B], loss[:B], state_err[B] if state_err is not None else None,
+                       state_err[:B] if state_err is not None else None, count)
+
+
+_zero_cache = {}
+
+
+def _zeros(dev, n: int) -> torch.Tensor:
+    """n fp32 zeros that are never written (the absent half of an upstream gradient); fresh ones while a stream is capturing."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.zeros(n, dtype=torch.float32, device=dev)
+    key = (dev.type, dev.index, n)
+    if key not in _zero_cache:
+        _zero_cache[key] = torch.zeros(n, dtype=torch.float32, device=dev)
+    return _zero_cache[key]
+
+
+class _FrameLossesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net_out, target, node_type, free_types, rows_per_frame, state):
+        ctx.set_materialize_grads(False)
+        loss, state_err, count, saved = _frame_losses_launch(net_out.detach(), target.detach(), node_type, free_types, rows_per_frame,
+                                                             state)
+        ctx.cfg = saved + (count, net_out, target)
+        out = _split_losses(loss, state_err, count)
+        ctx.mark_non_differentiable(*(t for t in out[2:] if t is not None))
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_frames, *unused):
+        x, tgt, nt, ldt, free_mask, per_frame, count, net_out, target = ctx.cfg
+        want_net, want_tgt = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g_loss is None and g_frames is None) or not (want_net or want_tgt):
+            return (None,) * 6
+        dev, (rows, F) = x.device, x.shape
+        B = rows // per_frame
+        g = torch.cat([g_frames.to(dev).float().reshape(B) if g_frames is not None else _zeros(dev, B),
+                       g_loss.to(dev).float().reshape(1) if g_loss is not None else _zeros(dev, 1)])
+        d_net = torch.empty(rows, F, dtype=torch.float32, device=dev) if want_net else None
+        d_tgt = torch.empty(rows, F, dtype=torch.float32, device=dev) if want_tgt else None
+        _lib.check(_lib.lib().hgn_frame_losses_bwd(
+            x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows, per_frame, count.data_ptr(),
+            g.data_ptr(), _ptr(d_net), _ld(d_net), _ptr(d_tgt), _ld(d_tgt), _lib.stream_ptr()), 'hgn_frame_losses_bwd')
+        return _like(d_net, net_out), _like(d_tgt, target), None, None, None, None
+
+
+def frame_losses(net_out: torch.Tensor, target: torch.Tensor, node_type: torch.Tensor, free_types, rows_per_frame=None,
+                 state=None) -> FrameLosses:
+    """The reference's masked MSE (flag.py:150-152: MSELoss()(target[mask], output[mask]), mask = the rows whose node type is listed
+    in ``free_types``) per frame of a batch and over all rows, on the device, in two launches and without a host read
+    (hgn_frame_losses).  ``net_out`` / ``target`` [rows, F] hold rows / rows_per_frame frames of ``rows_per_frame`` rows each (None:
+    one frame); views with a row stride are taken as they are.  ``state`` = (normalizer, cur, d, ca, prev, cp, state_target) adds the
+    error of the updated state ``ca*cur + normalizer.inverse(net_out)[:, :d] + cp*prev`` (``prev`` may be None; the bits of
+    rollout_advance / the model's `update`) against ``state_target`` [rows, d]: what validation_step reports beside the loss.
+    Sums are doubles in a fixed order (include/hgn_features.h): runs are bit-equal, and a frame's entries depend on its own rows
+    alone.  A frame without a free row has NaN entries, as the reference's mean over no element.
+    -> FrameLosses(loss, per_frame [B], state_error, state_per_frame [B], count [B+1]).  When ``net_out`` or ``target`` requires grad
+    the call is an autograd node: ``loss`` and ``per_frame`` are differentiable through ONE launch (hgn_frame_losses_bwd), the other
+    outputs are not (the state error is an evaluation figure); an output nobody differentiates costs nothing in the backward pass."""
+    _lib.require_gpu(net_out)
+    if _needs_grad(net_out, target):
+        return FrameLosses(*_FrameLossesFn.apply(net_out, target, node_type, tuple(free_types), rows_per_frame, state))
+    loss, state_err, count, _ = _frame_losses_launch(net_out.detach(), target.detach(), node_type, free_types, rows_per_frame, state)
+    return _split_losses(loss, state_err, count)
 
 
 def radius_edges(pos: torch.Tensor, node_type: torch.Tensor, radius: float, sender_type: int, receiver_type: int,

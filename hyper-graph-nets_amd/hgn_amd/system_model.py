@@ -264,11 +264,37 @@ class AbstractSystemModel(nn.Module):
         t = data_frame['node_type'].to(device)[:, 0]
         return reduce(torch.logical_or, [torch.eq(t, value) for value in self._LOCKSTEP.free_types])
 
+    # False: the training loss is the torch sequence `_masked_mse` behind `_loss_mask`, launch for launch what it was.  True (opt-in):
+    # `training_step` and every step of `unrolled_training_step` take features.frame_losses(...).loss -- two HIP launches forward, one
+    # backward, double sums in a fixed order.  A plain class-level value: a model unpickled from an older checkpoint reads False.
+    loss_kernel = False
+
+    def _training_loss(self, target_normalized: Tensor, network_output: Tensor, data_frame: Dict) -> Tensor:
+        if self.loss_kernel:
+            return features.frame_losses(network_output, target_normalized, data_frame['node_type'], self._LOCKSTEP.free_types).loss
+        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
+
     def training_step(self, graph, data_frame):
         """flag.py:146-154, cylinder.py:123-136, plate.py:218-228."""
         network_output = self(graph)
         target_normalized = self.get_target(data_frame)
-        return _masked_mse(target_normalized, network_output, self._loss_mask(data_frame))
+        return self._training_loss(target_normalized, network_output, data_frame)
+
+    def training_step_batch(self, graph, data_frame, n_graphs: int) -> Tuple[Tensor, Tensor]:
+        """Not in the reference, whose batched training step returns one scalar while it logs a loss per trajectory
+        (MeshSimulator.py:151-156): `training_step` for the union graph of ``n_graphs`` frames (build_graph_batch /
+        expand_graph_batch) and the flattened frames (`flatten_frames`), always through features.frame_losses.
+        -> (loss over all rows, the loss of every frame [B] detached).  ``loss`` is what `training_step` returns with `loss_kernel =
+        True`: the same squares summed in double, grouped by frame here and by 256 rows there, and rounded to fp32 once -- equal
+        bits unless the two double sums fall on either side of an fp32 rounding boundary."""
+        network_output = self(graph)
+        target_normalized = self.get_target(data_frame)
+        rows = network_output.shape[0]
+        if int(n_graphs) < 1 or rows % int(n_graphs):
+            raise ValueError(f'training_step_batch: {rows} rows do not split into {n_graphs} frames')
+        res = features.frame_losses(network_output, target_normalized, data_frame['node_type'], self._LOCKSTEP.free_types,
+                                    rows // int(n_graphs))
+        return res.loss, res.per_frame.detach()
 
     @torch.no_grad()
     def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
@@ -281,6 +307,56 @@ class AbstractSystemModel(nn.Module):
         new_state = updated if torch.is_tensor(updated) else updated[0]      # the flag's update returns the state alone
         state_error = _masked_mse(data_frame[self._LOCKSTEP.target].to(device), new_state, mask).item()
         return loss, state_error
+
+    @torch.no_grad()
+    def validation_step_batch(self, graph: MultiGraph, data_frame: Dict, n_graphs: int) -> Tuple[Tensor, Tensor]:
+        """Not in the reference, which validates one frame per call (MeshSimulator.py:295-297): `validation_step` for the union graph
+        of ``n_graphs`` frames (build_graph_batch / expand_graph_batch) and the flattened frames (`flatten_frames`).
+        -> (loss [B], state_error [B]): float32 device tensors, entry b = what `validation_step` returns for frame b; no host read.
+        The network, `get_target(flat, False)` and ONE features.frame_losses call, which forms the updated state with the constants
+        of `_LOCKSTEP` (the bits of `update`) and compares it against the `_LOCKSTEP.target` series on the free rows."""
+        ls = self._LOCKSTEP
+        prediction = self(graph)
+        target_normalized = self.get_target(data_frame, False)
+        rows = prediction.shape[0]
+        if int(n_graphs) < 1 or rows % int(n_graphs):
+            raise ValueError(f'validation_step_batch: {rows} rows do not split into {n_graphs} frames')
+        res = features.frame_losses(prediction, target_normalized, data_frame['node_type'], ls.free_types, rows // int(n_graphs),
+                                    state=(self._output_normalizer, data_frame[ls.state], ls.d, ls.ca,
+                                           data_frame[ls.prev] if ls.prev else None, ls.cp, data_frame[ls.target]))
+        return res.per_frame, res.state_per_frame
+
+    @torch.no_grad()
+    def one_step_errors(self, trajectory: Dict[str, Tensor], batch=None, num_timesteps=None) -> Tensor:
+        """What the reference's one_step_evaluator collects for one trajectory (MeshSimulator.py:292-297): [loss, state_error] of
+        every frame -> [T, 2] float32 on the CPU.  ``trajectory``: [T, ...] series (`cells` and `mesh_pos` per frame, as a dataset
+        yields them); ``num_timesteps``: only the first that many frames.
+        ``batch`` = M > 0 on a model without a connector and without a graph balancer: consecutive chunks of M frames (the last one
+        may be shorter) go through build_graph_batch(., False), expand_graph_batch(., M', first, T, False) and
+        `validation_step_batch`; the figures stay on the device until ONE copy at the end.  The trajectory must be one mesh (`cells`
+        of frame 0 is used for all frames).  Otherwise -- ``batch`` None or 0, or a model with a connector or a balancer, whose
+        clusters and balance edges are per frame (the reason `n_step_computation` gives) -- the reference's own loop: build_graph,
+        expand_graph(., t, T, False) and `validation_step` frame by frame, two host reads each.
+        Semantic difference of the batched route, the one build_graph_batch documents: a normaliser that accumulates on every build
+        (the flag's node-dynamic one) accumulates once per chunk, with the statistics of the chunk's frames, not once per frame."""
+        frames = trajectory['cells'].shape[0] if num_timesteps is None else int(num_timesteps)
+        if batch and int(batch) > 0 and not (self._rmp or self._balancer):
+            series = {name: t[:frames].to(device) for name, t in trajectory.items() if name != 'cells'}
+            cells = trajectory['cells'][0]
+            chunks = []
+            for first in range(0, frames, int(batch)):
+                chunk = {name: t[first:first + int(batch)] for name, t in series.items()}
+                chunk['cells'] = cells
+                count = chunk['node_type'].shape[0]
+                graph = self.expand_graph_batch(self.build_graph_batch(chunk, False), count, first, frames, False)
+                chunks.append(torch.stack(self.validation_step_batch(graph, self.flatten_frames(chunk), count), dim=1))
+            return torch.cat(chunks).cpu() if chunks else torch.zeros(0, 2)
+        rows = []
+        for t in range(frames):
+            frame = {name: series[t] for name, series in trajectory.items()}
+            graph = self.expand_graph(self.build_graph(frame, False), t, frames, False)
+            rows.append(list(self.validation_step(graph, frame)))
+        return torch.tensor(rows, dtype=torch.float32).reshape(frames, 2)
 
     # ---- evaluation helpers shared by the three models ------------------------------------------------------------
     @staticmethod
@@ -474,7 +550,7 @@ class AbstractSystemModel(nn.Module):
             graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate)
             flat = self.flatten_frames(frame)
             output = self(graph)
-            losses.append(_masked_mse(self.get_target(flat, accumulate), output, self._loss_mask(flat)))
+            losses.append(self._training_loss(self.get_target(flat, accumulate), output, flat))
             if t + 1 == n_steps:
                 break
             cur = flat[ls.state]

@@ -22,6 +22,8 @@
  *   migration/normalizer.py:40-71    Normalizer.forward / inverse / _accumulate -> hgn_col_stats,
  *                                                                              hgn_normalizer_update, hgn_normalize
  *   data/preprocessing.py:84-98      Preprocessing._add_noise, per frame         -> hgn_training_noise (a batch of frames)
+ *   model/flag.py:146-167, cylinder.py:123-153, plate.py:218-244
+ *                                    the masked MSE of training / validation_step -> hgn_frame_losses (per frame of a batch), _bwd
  */
 #ifndef HGN_FEATURES_H
 #define HGN_FEATURES_H
@@ -258,6 +260,68 @@ int hgn_training_noise(const float* x, int64_t ldx, int d, const int64_t* node_t
                        int64_t rows, int64_t rows_per_frame, const int64_t* frame_ids /* nullable */, uint64_t seed,
                        uint64_t draw, float std_, const float* target /* nullable */, int64_t ld_tgt, float target_scale,
                        float* out_x, int64_t ld_ox, float* out_target /* null iff target is */, int64_t ld_ot, void* stream);
+
+/* ---- per-frame losses of a batch of frames (flag.py:146-167, cylinder.py:123-153, plate.py:218-244: training_step and
+ * validation_step; algorithms/MeshSimulator.py:151-156 "loss per trajectory", :295-297 [loss, pos_error] per frame) --------------
+ * The masked mean squared error of the reference -- MSELoss()(target[mask], output[mask]), and for validation the same error of the
+ * updated state -- for every frame of a batch and for the batch as a whole, without a host read.  The rows are B = rows /
+ * rows_per_frame frames of rows_per_frame nodes each.
+ * In:  net_out [rows, ld_out] (the network output, F columns), target [rows, ld_tgt] (the normalised target, as get_target returns
+ *      it), node_type int64 with element stride ldt; a row is free when its type lies in [0, 32) and that bit of free_mask is set
+ *      (the convention of hgn_rollout_advance).  Every matrix has its own row stride.
+ *      State part, given whole or not at all: acc_sum / acc_sumsq / acc_count / eps of the output normaliser, cur [rows, ld_cur]
+ *      (d columns), ca, prev (nullable) [rows, ld_prev] with cp, state_target [rows, ld_st] (d columns).  Without it d, ca, cp, eps
+ *      and the strides of the absent matrices are not read.
+ * Out: loss [B+1] float, state_err [B+1] float (null exactly when there is no state part), count [B+1] int64.  Entry f < B belongs
+ *      to frame f, entry B to all rows.  With n_f = the number of free rows of frame f:
+ *        S_f = sum over the free rows r of f, c < F, of ((double)net_out[r,c] - (double)target[r,c])^2
+ *        loss[f] = (float)(S_f / ((double)n_f * F))          loss[B] = (float)(sum_f S_f / ((double)(sum_f n_f) * F))
+ *        x = net_out[r,c] * max(std[c], eps) + mean[c],  v = (ca * cur[r,c] + x) + cp * prev[r,c]   for c < d, in fp32, every product
+ *            and sum rounded on its own, the last term left out without prev: the expressions of hgn_rollout_advance, so v has the
+ *            bits of the model's `update`
+ *        E_f = sum over the free rows r of f, c < d, of ((double)v - (double)state_target[r,c])^2
+ *        state_err[f] = (float)(E_f / ((double)n_f * d)),   state_err[B] likewise from the sums over all frames
+ *        count[f] = n_f,  count[B] = sum_f n_f
+ *      One rounding to fp32 per entry.  n_f = 0 gives IEEE 0 / 0 = NaN in that entry (what the reference's mean over no element
+ *      gives) and leaves every other per-frame entry as it is.  Rows that are not free are not read beyond their type.
+ * Order: a frame is cut into chunks of HGN_LOSS_CHUNK_ROWS rows counted from the frame's own first row; one thread per row adds the
+ * squares of its row in ascending column order; the partial sums are doubles and meet in a fixed order: the lanes of a wavefront by
+ * halving strides, the four wavefronts of a chunk as (0 + 1) + (2 + 3), the chunks of a frame in ascending order, and for entry B
+ * the frames in ascending order.  No atomics.  Hence: two runs give equal bits; and loss[f], state_err[f] and count[f] depend on the
+ * rows of frame f alone -- not on the frame's place in the batch and not on B.
+ * At most two launches (partials, then one workgroup that finalises); the partials live in the caller's workspace
+ * (hgn_frame_losses_workspace_bytes; 8-byte aligned).  Plain vector loads and stores.
+ * rows = 0: no-op.  HGN_E_INVALID before any launch: F outside 1..HGN_MAX_FEATURE_WIDTH, rows outside [0, 2^31), rows_per_frame < 1
+ * or not dividing rows, a state part given in part (prev without the rest included), state_err null with a state part or given
+ * without one, d outside 1..F with a state part, a row stride smaller than its row (ldt < 1), null net_out / target / node_type /
+ * loss / count with rows > 0, a workspace that is null, misaligned or too small. */
+#define HGN_LOSS_CHUNK_ROWS 256 /* rows of a frame per chunk (= threads of a workgroup of the partial pass) */
+int hgn_frame_losses_workspace_bytes(int64_t rows, int64_t rows_per_frame, size_t* bytes);
+int hgn_frame_losses(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F, const int64_t* node_type,
+                     int64_t ldt, uint32_t free_mask, int64_t rows, int64_t rows_per_frame, const float* acc_sum,
+                     const float* acc_sumsq, const float* acc_count, float eps, const float* cur, int64_t ld_cur, int d, float ca,
+                     const float* prev /* nullable */, int64_t ld_prev, float cp, const float* state_target, int64_t ld_st,
+                     float* loss /*[B+1]*/, float* state_err /*[B+1] or null without a state part*/, int64_t* count /*[B+1]*/,
+                     void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- backward of the per-frame losses ------------------------------------------------------------------------------------------
+ * ONE launch, flat over [rows, F], 256 threads per block, no LDS, no atomics, equal bits on every run.  count [B+1] is the forward's;
+ * g [B+1] holds the upstream gradients of `loss` (nullable as a whole = all zero; the caller zero-fills entries that got none).
+ * Nothing flows through state_err: it is an evaluation figure, not a training loss.
+ *   free row of frame f:  w = (float)((double)g[f] / ((double)count[f] * F) + (double)g[B] / ((double)count[B] * F))
+ *                         d_net[r,c] = (2 * (net_out[r,c] - target[r,c])) * w     the difference and the product each rounded once in
+ *                                                                                fp32 (the doubling is exact)
+ *   any other row:        d_net[r,c] = 0
+ *   d_target[r,c] = -d_net[r,c]
+ * d_net [rows, ld_dnet] and d_target [rows, ld_dtgt] are each nullable, at least one must be given; every element of every output
+ * given is written exactly once, so the buffers need no initialisation.
+ * rows = 0: no-op.  HGN_E_INVALID before any launch: F outside 1..HGN_MAX_FEATURE_WIDTH, rows outside [0, 2^31), rows_per_frame < 1
+ * or not dividing rows, a row stride smaller than its row (ldt < 1), no output asked for, null net_out / target / node_type / count
+ * with rows > 0. */
+int hgn_frame_losses_bwd(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F, const int64_t* node_type,
+                         int64_t ldt, uint32_t free_mask, int64_t rows, int64_t rows_per_frame, const int64_t* count,
+                         const float* g /* nullable */, float* d_net, int64_t ld_dnet, float* d_target, int64_t ld_dtgt,
+                         void* stream);
 
 /* ---- backward of the connector's cluster mean (hierarchical_connector.py:39-45; rmp.py HierarchicalConnector.run, the line
  * `means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))`) ----------------------------------

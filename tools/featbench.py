@@ -12,7 +12,11 @@
   * with --noise, the seeded training noise alone: one launch per batch of B = 21 / 128 flag frames against the reference's torch
     sequence per frame (noise_timing).
 
-    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only | --noise]
+  * with --loss, the training loss (forward + backward) and one-step evaluation at 1 and at 128 flag frames: the torch sequence
+    `_masked_mse` and the per-frame validation_step loop against features.frame_losses and one_step_errors(batch=B), with the
+    device launches of both forms (loss_timing; profiles/frame_losses_time.md).
+
+    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only | --noise | --loss]
 Prints one JSON object.
 """
 import argparse
@@ -146,18 +150,117 @@ def noise_timing(rounds=20, warm=3):
     return out
 
 
+def _stats(ms):
+    mean = sum(ms) / len(ms)
+    return {'mean': mean, 'min': min(ms), 'max': max(ms), 'std': (sum((v - mean) ** 2 for v in ms) / len(ms)) ** 0.5}
+
+
+def _device_launches(fn):
+    """Kernel launches and device copies of one call of ``fn``, counted by torch's profiler; None where it records no device events."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        count = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
+        return count or None
+    except Exception:
+        return None
+
+
+def loss_timing(rounds=20, warm=4, inner=20):
+    """The training loss and one-step evaluation at 1 and at 128 frames of the 1 600-node flag mesh, the torch form of the parent
+    against the kernel form, alternating round by round in one process (host clock around a synchronised window of ``inner`` calls;
+    ms per call: mean, min, max and standard deviation over the timed rounds).
+      * loss forward + backward: `_loss_mask` + `_masked_mse` + autograd against features.frame_losses(...).loss, on a network output
+        that requires grad (the target does not: the single-step case);
+      * one-step evaluation: the per-frame loop over build_graph / validation_step (one_step_errors(batch=None), two host reads per
+        frame) against one_step_errors(batch=B): one union graph, one frame_losses call, one copy."""
+    from functools import reduce
+    from hgn_amd import features, synthetic, system_model
+    from hgn_amd.system_model import _masked_mse
+    host = [synthetic.flag_frame(seed=i, nx=40, ny=40) for i in range(4)]
+    free = system_model.FlagModel._LOCKSTEP.free_types
+    out = {}
+
+    def window(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    def alternate(forms, n):
+        ms = {k: [] for k in forms}
+        for r in range(warm + rounds):
+            for k, fn in forms.items():
+                t = window(fn, n)
+                if r >= warm:
+                    ms[k].append(t)
+        return ms
+
+    for B in (1, 128):
+        rows = B * 1600
+        gen = torch.Generator().manual_seed(B)
+        net = torch.randn(rows, 3, generator=gen).cuda().requires_grad_(True)
+        target = torch.randn(rows, 3, generator=gen).cuda()
+        node_type = torch.cat([host[i % 4]['node_type'] for i in range(B)]).cuda()
+
+        def torch_form():
+            t = node_type[:, 0]
+            mask = reduce(torch.logical_or, [torch.eq(t, value) for value in free])
+            net.grad = None
+            _masked_mse(target, net, mask).backward()
+            return net.grad
+
+        def kernel_form():
+            net.grad = None
+            features.frame_losses(net, target, node_type, free, 1600).loss.backward()
+            return net.grad
+        forms = {'torch sequence': torch_form, 'frame_losses': kernel_form}
+        gap = float((torch_form() - kernel_form()).abs().max() / torch_form().abs().max())
+        row = {'rows': rows, 'max gradient gap / max gradient': gap,
+               'device launches per call': {k: _device_launches(fn) for k, fn in forms.items()}}
+        row.update({f'{k} ms': _stats(v) for k, v in alternate(forms, inner).items()})
+        out[f'loss forward + backward, B={B}'] = row
+
+        model = system_model.FlagModel(dict(params('none', 16), message_passing_steps=15))
+        trajectory = {k: torch.stack([host[i % 4][k] for i in range(B)]).cuda() for k in host[0]}
+        with torch.no_grad():
+            model.build_graph(_frame_of(trajectory, 0), True)               # the normalisers see data once
+            model.get_target(_frame_of(trajectory, 0), True)
+        forms = {'validation_step loop': lambda: model.one_step_errors(trajectory), 'one_step_errors(batch=B)': lambda: model.one_step_errors(trajectory, batch=B)}
+        a, b = (fn() for fn in forms.values())
+        row = {'frames': B, 'max relative gap of the figures': float(((a - b).abs() / a.abs()).max()),
+               'device launches per call': {k: _device_launches(fn) for k, fn in forms.items()}}
+        row.update({f'{k} ms': _stats(v) for k, v in alternate(forms, 1 if B > 1 else 5).items()})
+        out[f'one-step evaluation, {B} frame(s), 15 message passing steps'] = row
+    return out
+
+
+def _frame_of(trajectory, t):
+    return {k: v[t] for k, v in trajectory.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=50)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--batched-only', action='store_true', help='only the per-frame against batched build / expand comparison')
     ap.add_argument('--noise', action='store_true', help='only the training noise: one launch per batch against the torch sequence per frame')
+    ap.add_argument('--loss', action='store_true', help='only the loss: the torch sequence and the per-frame validation loop against frame_losses / one_step_errors(batch)')
     a = ap.parse_args()
     from hgn_amd import features, synthetic, system_model
     from hgn_amd.normalizer import Normalizer
     res = {}
     if a.noise:
         print(json.dumps({'training noise': noise_timing()}))
+        return
+    if a.loss:
+        print(json.dumps({'frame losses': loss_timing()}))
         return
     if a.batched_only:
         print(json.dumps({'batched builds': batched_builds()}))
