@@ -452,6 +452,196 @@ __global__ void frame_losses_bwd_kernel(const float* __restrict__ net_out, long 
   if (d_target) d_target[r * ld_dt + c] = -v;
 }
 
+// ----------------------------------------------------------------------------------------------------------
+// ragged batches: B frames of N_0 .. N_{B-1} rows, frame f = rows [frame_ptr[f], frame_ptr[f+1]) of the union
+// ----------------------------------------------------------------------------------------------------------
+// frame_ptr [B+1] is the caller's device copy of the exclusive prefix of the frame sizes the entry validated on the host.  The kernels
+// below never trust it for an address: a bound read from it is clamped to [0, rows] and an end below its start gives an empty frame,
+// and the search returns a frame in [0, B), so a wrong array gives wrong figures and nothing else.
+__device__ __forceinline__ long ragged_bound(const int* __restrict__ frame_ptr, long i, long rows) {
+  const long v = frame_ptr[i];
+  return v < 0 ? 0 : (v > rows ? rows : v);
+}
+
+// the frame that owns row r: the last f in [0, B) with frame_ptr[f] <= r (reads entries 1 .. B-1 only)
+__device__ __forceinline__ long ragged_frame_of(const int* __restrict__ frame_ptr, long B, long r) {
+  long lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const long mid = (lo + hi + 1) >> 1;
+    if ((long)frame_ptr[mid] <= r) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// hgn_training_noise for a ragged batch: training_noise_kernel with (frame, node) found from frame_ptr -- the same counter, key and
+// Box-Muller, so the rows of a frame have the bits the uniform kernel gives that frame with the same frame id.
+__global__ void training_noise_ragged_kernel(const float* __restrict__ x, long ldx, int d, const int64_t* __restrict__ node_type,
+                                             long ldt, unsigned free_mask, long rows, const int* __restrict__ frame_ptr, long n_frames,
+                                             const int64_t* __restrict__ frame_ids, unsigned key0, unsigned key1, unsigned draw0,
+                                             unsigned draw1, float std_, const float* __restrict__ target, long ld_tgt,
+                                             float target_scale, float* __restrict__ out_x, long ld_ox,
+                                             float* __restrict__ out_target, long ld_ot) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const int64_t t = node_type[r * ldt];
+  const bool is_free = t >= 0 && t < 32 && ((free_mask >> (unsigned)t) & 1u);
+  float z[4] = {0.f, 0.f, 0.f, 0.f};
+  if (is_free) {
+    const long f = ragged_frame_of(frame_ptr, n_frames, r);
+    const unsigned node = (unsigned)(r - ragged_bound(frame_ptr, f, rows));
+    const unsigned fid = frame_ids ? (unsigned)frame_ids[f] : (unsigned)f;
+    unsigned w[4];
+    philox4x32_10(node, fid, draw0, draw1, key0, key1, w);
+    box_muller(w[0], w[1], z[0], z[1]);
+    if (d > 2) box_muller(w[2], w[3], z[2], z[3]);
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c >= d) break;
+    const float xv = x[r * ldx + c];
+    if (!is_free) {                                                 // a copy, bit for bit (-0.0 and NaN payloads included)
+      out_x[r * ld_ox + c] = xv;
+      if (target) out_target[r * ld_ot + c] = target[r * ld_tgt + c];
+      continue;
+    }
+    const float nz = std_ * z[c];                                   // plain products and sums, as in training_noise_kernel
+    out_x[r * ld_ox + c] = xv + nz;
+    if (target) {
+      const float scaled = target_scale * nz;
+      out_target[r * ld_ot + c] = target[r * ld_tgt + c] + scaled;
+    }
+  }
+}
+
+// hgn_frame_losses for a ragged batch.  Workgroup (f, k) of a grid of B x max_chunks takes chunk k of frame f, counted from the
+// frame's own first row; a workgroup past its frame's last chunk leaves at once and writes nothing (the finalising pass reads only
+// the chunks a frame has).  Per row and per workgroup the operations and their order are those of frame_losses_partial_kernel.
+__global__ __launch_bounds__(HGN_LOSS_CHUNK_ROWS) void frame_losses_ragged_partial_kernel(
+    const float* __restrict__ net_out, long ld_out, const float* __restrict__ target, long ld_tgt, int F,
+    const int64_t* __restrict__ node_type, long ldt, unsigned free_mask, long rows, const int* __restrict__ frame_ptr,
+    long max_chunks, const float* __restrict__ acc_sum, const float* __restrict__ acc_sumsq, const float* __restrict__ acc_count,
+    float eps, const float* __restrict__ cur, long ld_cur, int d, float ca, const float* __restrict__ prev, long ld_prev, float cp,
+    const float* __restrict__ state_target, long ld_st, double* __restrict__ part_s, double* __restrict__ part_e,
+    long long* __restrict__ part_n) {
+  __shared__ float mean[HGN_MAX_FEATURE_WIDTH], sd[HGN_MAX_FEATURE_WIDTH];
+  __shared__ double lds_s[HGN_LOSS_CHUNK_ROWS / 64], lds_e[HGN_LOSS_CHUNK_ROWS / 64];
+  __shared__ int lds_n[HGN_LOSS_CHUNK_ROWS / 64];
+  const int t = threadIdx.x;
+  const long f = (long)blockIdx.x / max_chunks;
+  const long k = (long)blockIdx.x - f * max_chunks;
+  const long first = ragged_bound(frame_ptr, f, rows);
+  const long frame_rows = ragged_bound(frame_ptr, f + 1, rows) - first;       // <= 0: an empty frame
+  if (k * HGN_LOSS_CHUNK_ROWS >= frame_rows) return;                          // uniform per workgroup, before any barrier
+  if (cur && t < d) {
+    const float safe = fmaxf(*acc_count, 1.f);
+    const float m = acc_sum[t] / safe;
+    mean[t] = m;
+    sd[t] = fmaxf(sqrtf(fabsf(acc_sumsq[t] / safe - m * m)), eps);
+  }
+  __syncthreads();
+  const long local = k * HGN_LOSS_CHUNK_ROWS + t;               // the row's place in its frame
+  bool is_free = false;
+  double s = 0.0, e = 0.0;
+  if (local < frame_rows) {
+    const long r = first + local;
+    const int64_t ty = node_type[r * ldt];
+    is_free = ty >= 0 && ty < 32 && ((free_mask >> (unsigned)ty) & 1u);
+    if (is_free) {
+      const float* o = net_out + r * ld_out;
+      const float* g = target + r * ld_tgt;
+      for (int c = 0; c < F; ++c) {
+        const double diff = (double)o[c] - (double)g[c];
+        s += diff * diff;
+      }
+      if (cur) {
+        for (int c = 0; c < d; ++c) {
+          const float x = o[c] * sd[c] + mean[c];                // Normalizer.inverse
+          float v = ca * cur[r * ld_cur + c] + 1.f * x;          // lincomb3 with cb = 1
+          if (prev) v = v + cp * prev[r * ld_prev + c];
+          const double diff = (double)v - (double)state_target[r * ld_st + c];
+          e += diff * diff;
+        }
+      }
+    }
+  }
+  const int n_wave = __popcll(__ballot(is_free));
+  if ((t & 63) == 0) lds_n[t >> 6] = n_wave;
+  const double S = loss_block_sum(s, lds_s);                     // its barrier also covers lds_n
+  const double E = loss_block_sum(e, lds_e);
+  if (t == 0) {
+    part_s[blockIdx.x] = S;
+    part_e[blockIdx.x] = E;
+    part_n[blockIdx.x] = (long long)((lds_n[0] + lds_n[1]) + (lds_n[2] + lds_n[3]));
+  }
+}
+
+// One workgroup: frame_losses_final_kernel with every frame's own number of chunks.
+__global__ __launch_bounds__(256) void frame_losses_ragged_final_kernel(const double* __restrict__ part_s,
+                                                                        const double* __restrict__ part_e,
+                                                                        const long long* __restrict__ part_n, long n_frames,
+                                                                        long rows, const int* __restrict__ frame_ptr, long max_chunks,
+                                                                        int F, int d, float* __restrict__ loss,
+                                                                        float* __restrict__ state_err, int64_t* __restrict__ count) {
+  __shared__ double fs[256], fe[256];
+  __shared__ long long fn[256];
+  __shared__ double tot_s, tot_e;
+  __shared__ long long tot_n;
+  const int t = threadIdx.x;
+  if (t == 0) { tot_s = 0.0; tot_e = 0.0; tot_n = 0; }
+  for (long base = 0; base < n_frames; base += 256) {
+    const long f = base + t;
+    double S = 0.0, E = 0.0;
+    long long n = 0;
+    if (f < n_frames) {
+      const long frame_rows = ragged_bound(frame_ptr, f + 1, rows) - ragged_bound(frame_ptr, f, rows);
+      long chunks = frame_rows > 0 ? (frame_rows + HGN_LOSS_CHUNK_ROWS - 1) / HGN_LOSS_CHUNK_ROWS : 0;
+      if (chunks > max_chunks) chunks = max_chunks;                 // (only a frame_ptr that is not the prefix of frame_rows)
+      for (long k = 0; k < chunks; ++k) {
+        const long b = f * max_chunks + k;
+        S += part_s[b]; E += part_e[b]; n += part_n[b];
+      }
+      loss[f] = (float)(S / ((double)n * (double)F));              // n = 0: IEEE 0 / 0 = NaN
+      if (state_err) state_err[f] = (float)(E / ((double)n * (double)d));
+      count[f] = (int64_t)n;
+    }
+    fs[t] = S; fe[t] = E; fn[t] = n;
+    __syncthreads();
+    const int live = (int)(n_frames - base < 256 ? n_frames - base : 256);
+    if (t == 0) { double a = tot_s; for (int j = 0; j < live; ++j) a += fs[j]; tot_s = a; }
+    if (t == 64) { double a = tot_e; for (int j = 0; j < live; ++j) a += fe[j]; tot_e = a; }
+    if (t == 128) { long long a = tot_n; for (int j = 0; j < live; ++j) a += fn[j]; tot_n = a; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    loss[n_frames] = (float)(tot_s / ((double)tot_n * (double)F));
+    if (state_err) state_err[n_frames] = (float)(tot_e / ((double)tot_n * (double)d));
+    count[n_frames] = (int64_t)tot_n;
+  }
+}
+
+// frame_losses_bwd_kernel with the row's frame found from frame_ptr: the same w, difference and product.
+__global__ void frame_losses_ragged_bwd_kernel(const float* __restrict__ net_out, long ld_out, const float* __restrict__ target,
+                                               long ld_tgt, int F, const int64_t* __restrict__ node_type, long ldt, unsigned free_mask,
+                                               long rows, const int* __restrict__ frame_ptr, long n_frames,
+                                               const int64_t* __restrict__ count, const float* __restrict__ g,
+                                               float* __restrict__ d_net, long ld_dn, float* __restrict__ d_target, long ld_dt) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * F) return;
+  const long r = i / F;
+  const int c = (int)(i - r * F);
+  const int64_t ty = node_type[r * ldt];
+  const bool is_free = ty >= 0 && ty < 32 && ((free_mask >> (unsigned)ty) & 1u);
+  float v = 0.f;
+  if (is_free && g) {
+    const long f = ragged_frame_of(frame_ptr, n_frames, r), B = n_frames;
+    const float w = (float)((double)g[f] / ((double)count[f] * (double)F) + (double)g[B] / ((double)count[B] * (double)F));
+    const float diff = net_out[r * ld_out + c] - target[r * ld_tgt + c];
+    v = (2.f * diff) * w;
+  }
+  if (d_net) d_net[r * ld_dn + c] = v;
+  if (d_target) d_target[r * ld_dt + c] = -v;
+}
+
 // Backward of the cluster mean of the connector (hierarchical_connector.py:39-45; rmp.py: `means_all = ...` in
 // HierarchicalConnector.run) with respect to the node rows.  Node-parallel, flat over [rows, D]: thread (n, c) walks row n's own
 // memberships q in [node_rowptr[n], node_rowptr[n+1]) in that order -- j = node_items[q] is a position of the member list, s =
@@ -584,6 +774,63 @@ __global__ void graph_offsets_kernel(const int* __restrict__ offsets, long n_gra
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b > n_graphs) return;
   graph_offsets[b] = offsets[b * N];
+}
+
+// The same query over the disjoint union of graphs of different sizes: sender row s finds its graph b from frame_ptr (uniform per
+// wave) and sweeps only the receivers [frame_ptr[b], frame_ptr[b+1]) -- sum_b N_b^2 / 64 chunk iterations, and no pair crosses a
+// graph boundary.  Every graph has its own mesh: the neighbour CSR is that of the union, rows and entries in union ids.
+template <bool FILL>
+__global__ void radius_edges_ragged_kernel(const float* __restrict__ pos, long ld, int d,
+                                           const int64_t* __restrict__ node_type, long ldt, long rows,
+                                           const int* __restrict__ frame_ptr, long n_graphs, float radius, int sender_type,
+                                           int receiver_type, const int* __restrict__ nbr_rowptr, const int* __restrict__ nbr,
+                                           int* __restrict__ counts, const int* __restrict__ offsets,
+                                           int64_t* __restrict__ senders, int64_t* __restrict__ receivers) {
+  const int lane = threadIdx.x & 63;
+  const long s = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (s >= rows) return;
+  const bool active = sender_type < 0 || node_type[s * ldt] == sender_type;      // uniform per wave
+  if (!active) { if (!FILL && lane == 0) counts[s] = 0; return; }
+  const long b = ragged_frame_of(frame_ptr, n_graphs, s);
+  const long g0 = ragged_bound(frame_ptr, b, rows), g1 = ragged_bound(frame_ptr, b + 1, rows);   // the sender's graph, inside [0, rows]
+  float ps[3];
+  for (int i = 0; i < 3; ++i) ps[i] = i < d ? pos[s * ld + i] : 0.f;
+  const int nb0 = nbr_rowptr ? nbr_rowptr[s] : 0, nb1 = nbr_rowptr ? nbr_rowptr[s + 1] : 0;
+  long base = FILL ? offsets[s] : 0;
+  int total = 0;
+  for (long r0 = g0; r0 < g1; r0 += 64) {
+    const long r = r0 + lane;                        // union id of the receiver, < g1 <= rows checked before any read
+    bool hit = false;
+    if (r < g1 && r != s && (receiver_type < 0 || node_type[r * ldt] == receiver_type)) {
+      float q = 0.f;
+      for (int i = 0; i < 3; ++i) {
+        const float df = i < d ? ps[i] - pos[r * ld + i] : 0.f;
+        q = q + df * df;
+      }
+      hit = sqrtf(q) < radius;
+      if (hit)
+        for (int k = nb0; k < nb1; ++k)
+          if (nbr[k] == (int)r) { hit = false; break; }
+    }
+    const unsigned long long m = __ballot(hit);
+    if (FILL && hit) {
+      const int before = __popcll(m & ((1ULL << lane) - 1ULL));
+      senders[base + before] = s;
+      receivers[base + before] = r;
+    }
+    const int c = __popcll(m);
+    base += c;
+    total += c;
+  }
+  if (!FILL && lane == 0) counts[s] = total;
+}
+
+// graph_offsets[b] = offsets[frame_ptr[b]] for b = 0 .. n_graphs (the last entry is the total)
+__global__ void graph_offsets_ragged_kernel(const int* __restrict__ offsets, const int* __restrict__ frame_ptr, long n_graphs,
+                                            long rows, int* __restrict__ graph_offsets) {
+  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b > n_graphs) return;
+  graph_offsets[b] = offsets[ragged_bound(frame_ptr, b, rows)];
 }
 
 // ----------------------------------------------------------------------------------------------------------
@@ -1126,6 +1373,124 @@ extern "C" int hgn_frame_losses_bwd(const float* net_out, int64_t ld_out, const 
   return hgn_check_launch("hgn_frame_losses_bwd");
 }
 
+// The host half of a ragged batch: -> the largest frame, or -1 when the array is refused (null, n_frames < 1, an entry < 1, a sum
+// that differs from rows, rows > max_rows).  Every ragged entry calls it before it launches anything.
+static int64_t ragged_max_rows(int64_t rows, const int64_t* frame_rows, int64_t n_frames, int64_t max_rows) {
+  if (!frame_rows || n_frames < 1 || rows < 1 || rows > max_rows || n_frames > rows) return -1;
+  int64_t sum = 0, largest = 0;
+  for (int64_t f = 0; f < n_frames; ++f) {
+    const int64_t n = frame_rows[f];
+    if (n < 1 || n > rows - sum) return -1;
+    sum += n;
+    if (n > largest) largest = n;
+  }
+  return sum == rows ? largest : -1;
+}
+
+#define HGN_RAGGED_SIZES "0 < rows < 2^31, n_frames >= 1, every frame_rows[f] >= 1, their sum = rows, frame_rows and frame_ptr not null"
+
+// -> the workgroups of the partial pass (n_frames * the chunks of the largest frame), or -1 for what the entries refuse
+static int64_t ragged_loss_chunks(int64_t rows, const int64_t* frame_rows, int64_t n_frames, int64_t* max_chunks) {
+  const int64_t largest = ragged_max_rows(rows, frame_rows, n_frames, 0x7fffffff);
+  if (largest < 0) return -1;
+  *max_chunks = (largest + HGN_LOSS_CHUNK_ROWS - 1) / HGN_LOSS_CHUNK_ROWS;
+  return n_frames > 0x7fffffffLL / *max_chunks ? -1 : n_frames * *max_chunks;
+}
+
+extern "C" int hgn_training_noise_ragged(const float* x, int64_t ldx, int d, const int64_t* node_type, int64_t ldt, uint32_t free_mask,
+                                         int64_t rows, const int64_t* frame_rows, const int32_t* frame_ptr, int64_t n_frames,
+                                         const int64_t* frame_ids, uint64_t seed, uint64_t draw, float std_, const float* target,
+                                         int64_t ld_tgt, float target_scale, float* out_x, int64_t ld_ox, float* out_target,
+                                         int64_t ld_ot, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (d < 1 || d > 4 || !frame_ptr || ragged_max_rows(rows, frame_rows, n_frames, 0x7fffffff) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise_ragged: bad sizes (1 <= d <= 4, " HGN_RAGGED_SIZES ")");
+  if ((target == nullptr) != (out_target == nullptr))
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise_ragged: target and out_target must both be given or both be null");
+  if (ldx < d || ld_ox < d || ldt < 1 || (target && (ld_tgt < d || ld_ot < d)))
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise_ragged: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (!(std_ >= 0.f) || std_ > 3.4028234e38f)
+    return hgn_fail(HGN_E_INVALID, "hgn_training_noise_ragged: the standard deviation must be finite and not negative");
+  if (!x || !node_type || !out_x) return hgn_fail(HGN_E_INVALID, "hgn_training_noise_ragged: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  hipLaunchKernelGGL(training_noise_ragged_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, x, (long)ldx, d,
+                     node_type, (long)ldt, (unsigned)free_mask, (long)rows, frame_ptr, (long)n_frames, frame_ids,
+                     (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), (unsigned)(draw & 0xffffffffu), (unsigned)(draw >> 32),
+                     std_, target, (long)ld_tgt, target_scale, out_x, (long)ld_ox, out_target, (long)ld_ot);
+  return hgn_check_launch("hgn_training_noise_ragged");
+}
+
+extern "C" int hgn_frame_losses_ragged_workspace_bytes(int64_t rows, const int64_t* frame_rows, int64_t n_frames, size_t* bytes) {
+  int64_t max_chunks = 0;
+  const int64_t chunks = ragged_loss_chunks(rows, frame_rows, n_frames, &max_chunks);
+  if (!bytes || chunks < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged_workspace_bytes: bad sizes (0 < rows < 2^31, n_frames >= 1, every "
+                                   "frame_rows[f] >= 1, their sum = rows, n_frames * chunks of the largest frame < 2^31)");
+  *bytes = (size_t)chunks * 3 * sizeof(double);
+  return HGN_OK;
+}
+
+extern "C" int hgn_frame_losses_ragged(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                                       const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows,
+                                       const int64_t* frame_rows, const int32_t* frame_ptr, int64_t n_frames, const float* acc_sum,
+                                       const float* acc_sumsq, const float* acc_count, float eps, const float* cur, int64_t ld_cur,
+                                       int d, float ca, const float* prev, int64_t ld_prev, float cp, const float* state_target,
+                                       int64_t ld_st, float* loss, float* state_err, int64_t* count, void* workspace,
+                                       size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t max_chunks = 0;
+  const int64_t chunks = ragged_loss_chunks(rows, frame_rows, n_frames, &max_chunks);
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || !frame_ptr || chunks < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: bad sizes (1 <= F <= 32, " HGN_RAGGED_SIZES
+                                   ", n_frames * chunks of the largest frame < 2^31)");
+  const int given = (acc_sum != nullptr) + (acc_sumsq != nullptr) + (acc_count != nullptr) + (cur != nullptr) + (state_target != nullptr);
+  if ((given != 0 && given != 5) || (given == 0 && prev))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: the state part (statistics, cur, state_target; prev optional) must be given whole or not at all");
+  const bool with_state = given == 5;
+  if (with_state != (state_err != nullptr))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: state_err must be given exactly when the state part is");
+  if (with_state && (d < 1 || d > F)) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: bad state width (1 <= d <= F)");
+  if (ld_out < F || ld_tgt < F || ldt < 1 || (with_state && (ld_cur < d || ld_st < d || (prev && ld_prev < d))))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (!net_out || !target || !node_type || !loss || !count) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: null pointer");
+  if (!workspace || ((uintptr_t)workspace & 7)) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: null or misaligned workspace");
+  if (ws_bytes < (size_t)chunks * 3 * sizeof(double))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged: workspace too small (hgn_frame_losses_ragged_workspace_bytes)");
+  ProfScope ps(13, (double)rows, stream);
+  double* part_s = (double*)workspace;
+  double* part_e = part_s + chunks;
+  long long* part_n = (long long*)(part_e + chunks);
+  hipLaunchKernelGGL(frame_losses_ragged_partial_kernel, dim3((unsigned)chunks), dim3(HGN_LOSS_CHUNK_ROWS), 0, stream, net_out,
+                     (long)ld_out, target, (long)ld_tgt, F, node_type, (long)ldt, (unsigned)free_mask, (long)rows, frame_ptr,
+                     (long)max_chunks, acc_sum, acc_sumsq, acc_count, eps, cur, (long)ld_cur, d, ca, prev, (long)ld_prev, cp,
+                     state_target, (long)ld_st, part_s, part_e, part_n);
+  hipLaunchKernelGGL(frame_losses_ragged_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)part_s, (const double*)part_e,
+                     (const long long*)part_n, (long)n_frames, (long)rows, frame_ptr, (long)max_chunks, F, with_state ? d : 1, loss,
+                     state_err, count);
+  return hgn_check_launch("hgn_frame_losses_ragged");
+}
+
+extern "C" int hgn_frame_losses_ragged_bwd(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                                           const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows,
+                                           const int64_t* frame_rows, const int32_t* frame_ptr, int64_t n_frames,
+                                           const int64_t* count, const float* g, float* d_net, int64_t ld_dnet, float* d_target,
+                                           int64_t ld_dtgt, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (F < 1 || F > HGN_MAX_FEATURE_WIDTH || !frame_ptr || ragged_max_rows(rows, frame_rows, n_frames, 0x7fffffff) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged_bwd: bad sizes (1 <= F <= 32, " HGN_RAGGED_SIZES ")");
+  if (ld_out < F || ld_tgt < F || ldt < 1 || (d_net && ld_dnet < F) || (d_target && ld_dtgt < F))
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged_bwd: bad strides (a row stride is smaller than its row, or ldt < 1)");
+  if (!d_net && !d_target)
+    return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged_bwd: no output asked for (d_net and d_target are both null)");
+  if (!net_out || !target || !node_type || !count) return hgn_fail(HGN_E_INVALID, "hgn_frame_losses_ragged_bwd: null pointer");
+  ProfScope ps(13, (double)rows, stream);
+  const int64_t n = rows * F;
+  hipLaunchKernelGGL(frame_losses_ragged_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, net_out, (long)ld_out,
+                     target, (long)ld_tgt, F, node_type, (long)ldt, (unsigned)free_mask, (long)rows, frame_ptr, (long)n_frames, count,
+                     g, d_net, (long)ld_dnet, d_target, (long)ld_dtgt);
+  return hgn_check_launch("hgn_frame_losses_ragged_bwd");
+}
+
 extern "C" int hgn_member_mean_bwd(const float* d_mean, int64_t ld_dmean, int D, const int32_t* seg_rowptr, int64_t S,
                                   const int32_t* item_seg, const int32_t* node_rowptr, const int32_t* node_items, int64_t rows,
                                   int64_t M, float* d_data, int64_t ld, void* stream_) {
@@ -1285,6 +1650,72 @@ extern "C" int hgn_radius_edges_batch_fill(const float* pos, int64_t ld, int d, 
                      node_type, (long)ldt, (long)rows, (long)nodes_per_graph, radius, sender_type, receiver_type, nbr_rowptr, nbr,
                      (int*)nullptr, offsets, senders, receivers);
   return hgn_check_launch("hgn_radius_edges_batch_fill");
+}
+
+#define HGN_RAGGED_GRAPHS "0 < rows <= 0x7ffffffe, n_graphs >= 1, every frame_rows[b] >= 1, their sum = rows"
+
+extern "C" int hgn_radius_edges_ragged_workspace_bytes(int64_t rows, const int64_t* frame_rows, int64_t n_graphs, size_t* bytes) {
+  if (!bytes || ragged_max_rows(rows, frame_rows, n_graphs, 0x7ffffffe) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_workspace_bytes: bad size (" HGN_RAGGED_GRAPHS ")");
+  size_t t = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum<int*, int*>(nullptr, t, nullptr, nullptr, (int)(rows + 1));
+  *bytes = radius_batch_counts_bytes(rows) + up256(t) + 256;
+  return HGN_OK;
+}
+
+extern "C" int hgn_radius_edges_ragged_count(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                             int64_t rows, const int64_t* frame_rows, const int32_t* frame_ptr, int64_t n_graphs,
+                                             float radius, int sender_type, int receiver_type, const int32_t* nbr_rowptr,
+                                             const int32_t* nbr, int32_t* offsets, int32_t* graph_offsets, int64_t* total,
+                                             void* workspace, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!frame_ptr || ragged_max_rows(rows, frame_rows, n_graphs, 0x7ffffffe) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_count: bad batch shape (" HGN_RAGGED_GRAPHS ", frame_ptr not null)");
+  if (!radius_args_ok(pos, ld, d, node_type, ldt, rows, radius, nbr_rowptr, nbr))
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_count: bad argument");
+  if (!offsets || !total) return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_count: null output");
+  size_t need = 0;
+  if (hgn_radius_edges_ragged_workspace_bytes(rows, frame_rows, n_graphs, &need) != HGN_OK || !workspace || ws_bytes < need)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_count: workspace missing or too small");
+  *total = 0;
+  ProfScope ps(13, (double)rows, stream);
+  int* counts = (int*)workspace;
+  void* temp = (char*)workspace + radius_batch_counts_bytes(rows);
+  size_t tb = need - radius_batch_counts_bytes(rows);
+  if (hipMemsetAsync(counts, 0, (size_t)(rows + 1) * 4, stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_ragged_count memset");
+  hipLaunchKernelGGL(radius_edges_ragged_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, pos, (long)ld, d,
+                     node_type, (long)ldt, (long)rows, frame_ptr, (long)n_graphs, radius, sender_type, receiver_type, nbr_rowptr, nbr,
+                     counts, (const int*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
+  if (hipcub::DeviceScan::ExclusiveSum(temp, tb, counts, offsets, (int)(rows + 1), stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_ragged_count scan");
+  if (graph_offsets)
+    hipLaunchKernelGGL(graph_offsets_ragged_kernel, dim3((unsigned)((n_graphs + 256) / 256)), dim3(256), 0, stream,
+                       (const int*)offsets, frame_ptr, (long)n_graphs, (long)rows, graph_offsets);
+  int host_total = 0;
+  if (hipMemcpyAsync(&host_total, offsets + rows, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return hgn_check_launch("hgn_radius_edges_ragged_count readback");
+  *total = host_total;
+  return hgn_check_launch("hgn_radius_edges_ragged_count");
+}
+
+extern "C" int hgn_radius_edges_ragged_fill(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt,
+                                            int64_t rows, const int64_t* frame_rows, const int32_t* frame_ptr, int64_t n_graphs,
+                                            float radius, int sender_type, int receiver_type, const int32_t* nbr_rowptr,
+                                            const int32_t* nbr, const int32_t* offsets, int64_t* senders, int64_t* receivers,
+                                            void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!frame_ptr || ragged_max_rows(rows, frame_rows, n_graphs, 0x7ffffffe) < 0)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_fill: bad batch shape (" HGN_RAGGED_GRAPHS ", frame_ptr not null)");
+  if (!radius_args_ok(pos, ld, d, node_type, ldt, rows, radius, nbr_rowptr, nbr) || !offsets)
+    return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_fill: bad argument");
+  if (!senders || !receivers) return hgn_fail(HGN_E_INVALID, "hgn_radius_edges_ragged_fill: null output");
+  ProfScope ps(13, (double)rows, stream);
+  hipLaunchKernelGGL(radius_edges_ragged_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, pos, (long)ld, d,
+                     node_type, (long)ldt, (long)rows, frame_ptr, (long)n_graphs, radius, sender_type, receiver_type, nbr_rowptr, nbr,
+                     (int*)nullptr, offsets, senders, receivers);
+  return hgn_check_launch("hgn_radius_edges_ragged_fill");
 }
 
 extern "C" int hgn_forman_curvature(const float* A, const float* A2, const float* d_in, const float* d_out, int64_t N,

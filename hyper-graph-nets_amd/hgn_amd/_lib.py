@@ -228,6 +228,25 @@ _SIGS = {
     'hgn_frame_losses_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32,
                                        C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_void_p]),
+    # the ragged forms: frame_rows (host int64 [B]), frame_ptr (device int32 [B+1]), B in place of rows_per_frame / nodes_per_graph
+    'hgn_radius_edges_ragged_workspace_bytes': (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_size_t)]),
+    'hgn_radius_edges_ragged_count': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                                C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'hgn_radius_edges_ragged_fill': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                               C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hgn_training_noise_ragged': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int64,
+                                            C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float,
+                                            C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'hgn_frame_losses_ragged_workspace_bytes': (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_size_t)]),
+    'hgn_frame_losses_ragged': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32,
+                                          C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'hgn_frame_losses_ragged_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_uint32,
+                                              C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_member_mean_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'hgn_rel_edge_features_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,

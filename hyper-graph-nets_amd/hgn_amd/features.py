@@ -474,7 +474,56 @@ def advance_state(net_out: torch.Tensor, normalizer, cur: torch.Tensor, d: int, 
     return _advance_into_fresh(net_out, normalizer, cur, d, ca, prev, cp, node_type, free_types, fallback, inv_from)
 
 
-def _noise_into_fresh(x, node_type, free_types, std, seed, draw, target, target_scale, rows_per_frame, frame_ids):
+_frame_ptr_cache = {}
+_FRAME_PTR_CACHE_SIZE = 64
+
+
+class _Ragged(NamedTuple):
+    """A ragged batch as the C ABI takes it: B, the frame sizes as a host int64 array, their exclusive prefix as a device int32 [B+1]."""
+    B: int
+    host: object
+    ptr: torch.Tensor
+
+
+def _ragged(frame_rows, rows: int, dev, what: str) -> _Ragged:
+    """``frame_rows`` (a sequence of ints, every one >= 1, summing to ``rows``) -> _Ragged; the device prefix is built once per distinct
+    tuple and device and kept in a small cache (the oldest entry leaves when it is full)."""
+    sizes = tuple(int(n) for n in frame_rows)
+    if not sizes or min(sizes) < 1 or sum(sizes) != rows:
+        raise ValueError(f'{what}: frame_rows must be a non-empty sequence of row counts >= 1 that sum to the {rows} rows given, '
+                         f'got {len(sizes)} frames with {sum(sizes)} rows')
+    if rows >= 1 << 31:
+        raise ValueError(f'{what}: {rows} rows do not fit the int32 frame_ptr')
+    key = (sizes, dev.type, dev.index)
+    hit = _frame_ptr_cache.get(key)
+    if hit is None:
+        prefix = [0]
+        for n in sizes:
+            prefix.append(prefix[-1] + n)
+        hit = _Ragged(len(sizes), (C.c_int64 * len(sizes))(*sizes), torch.tensor(prefix, dtype=torch.int32, device=dev))
+        if len(_frame_ptr_cache) >= _FRAME_PTR_CACHE_SIZE:
+            _frame_ptr_cache.pop(next(iter(_frame_ptr_cache)))
+        _frame_ptr_cache[key] = hit
+    return hit
+
+
+def _one_split(what: str, rows_per_frame, frame_rows) -> None:
+    if rows_per_frame is not None and frame_rows is not None:
+        raise ValueError(f'{what}: give rows_per_frame (frames of equal size) or frame_rows (a ragged batch), not both')
+
+
+def _frame_ids_tensor(frame_ids, n_frames: int, dev):
+    """ids travel as int64 and are read modulo 2^32; a Python int up to 2^64 - 1 keeps its low 64 bits"""
+    if not torch.is_tensor(frame_ids):
+        frame_ids = torch.tensor([((int(i) + (1 << 63)) % (1 << 64)) - (1 << 63) for i in frame_ids], dtype=torch.int64)
+    frame_ids = _ids(frame_ids.reshape(-1), dev)
+    if frame_ids.shape[0] != n_frames:
+        raise ValueError(f'add_noise: {frame_ids.shape[0]} frame ids for {n_frames} frames')
+    return frame_ids
+
+
+def _noise_into_fresh(x, node_type, free_types, std, seed, draw, target, target_scale, rows_per_frame, frame_ids,
+                      frame_rows=None):
     dev = x.device
     shape, x = x.shape, _f32_rows(x)
     rows, d = x.shape
@@ -488,25 +537,25 @@ def _noise_into_fresh(x, node_type, free_types, std, seed, draw, target, target_
     if nt.shape[0] != rows:
         raise ValueError(f'add_noise: {nt.shape[0]} node types for {rows} rows')
     free_mask = _free_mask(free_types, 'add_noise')
+    ragged = _ragged(frame_rows, rows, dev, 'add_noise') if frame_rows is not None else None
     per_frame = max(rows, 1) if rows_per_frame is None else int(rows_per_frame)
-    if per_frame < 1 or rows % per_frame:
+    if ragged is None and (per_frame < 1 or rows % per_frame):
         raise ValueError(f'add_noise: {rows} rows do not split into frames of {rows_per_frame} rows')
     if frame_ids is not None:
-        # ids travel as int64 and are read modulo 2^32; a Python int up to 2^64 - 1 keeps its low 64 bits
-        if not torch.is_tensor(frame_ids):
-            frame_ids = torch.tensor([((int(i) + (1 << 63)) % (1 << 64)) - (1 << 63) for i in frame_ids], dtype=torch.int64)
-        frame_ids = _ids(frame_ids.reshape(-1), dev)
-        if frame_ids.shape[0] != rows // per_frame:
-            raise ValueError(f'add_noise: {frame_ids.shape[0]} frame ids for {rows // per_frame} frames')
+        frame_ids = _frame_ids_tensor(frame_ids, ragged.B if ragged else rows // per_frame, dev)
     seed, draw = int(seed), int(draw)
     if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 64):
         raise ValueError('add_noise: seed and draw must lie in [0, 2^64)')
     out_x = torch.empty(rows, d, dtype=torch.float32, device=dev)
     out_t = torch.empty(rows, d, dtype=torch.float32, device=dev) if target is not None else None
-    _lib.check(_lib.lib().hgn_training_noise(
-        x.data_ptr(), _ld(x), d, nt.data_ptr(), ldt, free_mask, rows, per_frame, _ptr(frame_ids), seed, draw, float(std),
-        _ptr(target), _ld(target), float(target_scale), out_x.data_ptr(), _ld(out_x), _ptr(out_t), _ld(out_t), _lib.stream_ptr()),
-        'hgn_training_noise')
+    tail = (_ptr(frame_ids), seed, draw, float(std), _ptr(target), _ld(target), float(target_scale), out_x.data_ptr(), _ld(out_x),
+            _ptr(out_t), _ld(out_t), _lib.stream_ptr())
+    if ragged is not None:
+        _lib.check(_lib.lib().hgn_training_noise_ragged(x.data_ptr(), _ld(x), d, nt.data_ptr(), ldt, free_mask, rows, ragged.host,
+                                                        ragged.ptr.data_ptr(), ragged.B, *tail), 'hgn_training_noise_ragged')
+    else:
+        _lib.check(_lib.lib().hgn_training_noise(x.data_ptr(), _ld(x), d, nt.data_ptr(), ldt, free_mask, rows, per_frame, *tail),
+                   'hgn_training_noise')
     return out_x.reshape(shape), (out_t.reshape(shape) if out_t is not None else None)
 
 
@@ -527,11 +576,13 @@ class _AddNoiseFn(torch.autograd.Function):
 
 
 def add_noise(x: torch.Tensor, node_type: torch.Tensor, free_types, std: float, seed: int, draw: int, target=None,
-              target_scale: float = 0.0, rows_per_frame=None, frame_ids=None):
+              target_scale: float = 0.0, rows_per_frame=None, frame_ids=None, frame_rows=None):
     """Seeded training noise for a batch of frames in one launch (hgn_training_noise; src/data/preprocessing.py:84-98,
     Preprocessing._add_noise, which runs once per frame): on the rows whose node type is listed in ``free_types``,
     ``noisy_x = x + n`` and ``noisy_target = target + target_scale * n`` with ``n = std * z``, z standard normal; every other row is
-    copied.  ``x`` [rows, d] (d = 1..4) holds rows / rows_per_frame frames of ``rows_per_frame`` rows each (None: one frame).
+    copied.  ``x`` [rows, d] (d = 1..4) holds rows / rows_per_frame frames of ``rows_per_frame`` rows each (None: one frame), or -- a
+    ragged batch, frames of different meshes -- ``frame_rows`` = the row count of every frame in turn (hgn_training_noise_ragged, one
+    launch as well; giving both raises ValueError).  A frame's rows get the samples this call gives that frame alone with its id.
     The generator is counter-based (Philox4x32-10, Box-Muller): the sample of a row is a function of ``seed``, ``draw`` (both in
     [0, 2^64); e.g. the training step), the frame's id (``frame_ids``: a sequence or an int64 tensor of one id per frame, read modulo
     2^32; None: 0, 1, ..) and the row's place in its frame -- not of the frame's place in the batch or of the rank that holds it.
@@ -540,8 +591,9 @@ def add_noise(x: torch.Tensor, node_type: torch.Tensor, free_types, std: float, 
     gradients back unchanged and launches nothing.
     Out of scope: the connector's `hyper_noise` keeps torch.normal; the reference's own src/data/preprocessing.py path through the
     shim is unchanged; noise inside captured graphs."""
+    _one_split('add_noise', rows_per_frame, frame_rows)
     _lib.require_gpu(x)
-    args = (node_type, tuple(free_types), float(std), seed, draw, float(target_scale), rows_per_frame, frame_ids)
+    args = (node_type, tuple(free_types), float(std), seed, draw, float(target_scale), rows_per_frame, frame_ids, frame_rows)
     if _needs_grad(x, target):
         return _AddNoiseFn.apply(x, target, args)
     return _noise_into_fresh(x, *args[:5], target, *args[5:])
@@ -557,7 +609,7 @@ class FrameLosses(NamedTuple):
     count: torch.Tensor
 
 
-def _frame_losses_launch(net_out, target, node_type, free_types, rows_per_frame, state):
+def _frame_losses_launch(net_out, target, node_type, free_types, rows_per_frame, state, frame_rows=None):
     """-> (loss [B+1], state_err [B+1] or None, count [B+1], what the backward launch needs)."""
     dev = net_out.device
     x = _f32_rows(net_out)
@@ -569,10 +621,11 @@ def _frame_losses_launch(net_out, target, node_type, free_types, rows_per_frame,
     if nt.shape[0] != rows:
         raise ValueError(f'frame_losses: {nt.shape[0]} node types for {rows} rows')
     free_mask = _free_mask(free_types, 'frame_losses')
+    ragged = _ragged(frame_rows, rows, dev, 'frame_losses') if frame_rows is not None else None
     per_frame = max(rows, 1) if rows_per_frame is None else int(rows_per_frame)
-    if per_frame < 1 or rows % per_frame:
+    if ragged is None and (per_frame < 1 or rows % per_frame):
         raise ValueError(f'frame_losses: {rows} rows do not split into frames of {rows_per_frame} rows')
-    B = rows // per_frame
+    B = ragged.B if ragged else rows // per_frame
     nz = cur = prev = state_target = None
     d, ca, cp, eps = 0, 0.0, 0.0, 0.0
     if state is not None:
@@ -587,18 +640,24 @@ def _frame_losses_launch(net_out, target, node_type, free_types, rows_per_frame,
                 raise ValueError(f'frame_losses: {name} must be [{rows}, {d}]')
     L = _lib.lib()
     nb = C.c_size_t(0)
-    _lib.check(L.hgn_frame_losses_workspace_bytes(rows, per_frame, C.byref(nb)), 'hgn_frame_losses_workspace_bytes')
+    if ragged is not None:
+        _lib.check(L.hgn_frame_losses_ragged_workspace_bytes(rows, ragged.host, B, C.byref(nb)), 'hgn_frame_losses_ragged_workspace_bytes')
+    else:
+        _lib.check(L.hgn_frame_losses_workspace_bytes(rows, per_frame, C.byref(nb)), 'hgn_frame_losses_workspace_bytes')
     ws = torch.empty(max(nb.value // 8, 1), dtype=torch.float64, device=dev)        # a fresh buffer per call: capturable
     loss = torch.empty(B + 1, dtype=torch.float32, device=dev)
     state_err = torch.empty(B + 1, dtype=torch.float32, device=dev) if state is not None else None
     count = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    _lib.check(L.hgn_frame_losses(
-        x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows, per_frame,
-        _ptr(nz._acc_sum) if nz is not None else None, _ptr(nz._acc_sum_squared) if nz is not None else None,
-        _ptr(nz._acc_count) if nz is not None else None, eps, _ptr(cur), _ld(cur), d, float(ca), _ptr(prev), _ld(prev), float(cp),
-        _ptr(state_target), _ld(state_target), loss.data_ptr(), _ptr(state_err), count.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-        _lib.stream_ptr()), 'hgn_frame_losses')
-    return loss, state_err, count, (x, tgt, nt, ldt, free_mask, per_frame)
+    head = (x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows)
+    tail = (_ptr(nz._acc_sum) if nz is not None else None, _ptr(nz._acc_sum_squared) if nz is not None else None,
+            _ptr(nz._acc_count) if nz is not None else None, eps, _ptr(cur), _ld(cur), d, float(ca), _ptr(prev), _ld(prev), float(cp),
+            _ptr(state_target), _ld(state_target), loss.data_ptr(), _ptr(state_err), count.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+            _lib.stream_ptr())
+    if ragged is not None:
+        _lib.check(L.hgn_frame_losses_ragged(*head, ragged.host, ragged.ptr.data_ptr(), B, *tail), 'hgn_frame_losses_ragged')
+    else:
+        _lib.check(L.hgn_frame_losses(*head, per_frame, *tail), 'hgn_frame_losses')
+    return loss, state_err, count, (x, tgt, nt, ldt, free_mask, per_frame, ragged)
 
 
 def _split_losses(loss, state_err, count) -> FrameLosses:
@@ -622,10 +681,10 @@ def _zeros(dev, n: int) -> torch.Tensor:
 
 class _FrameLossesFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net_out, target, node_type, free_types, rows_per_frame, state):
+    def forward(ctx, net_out, target, node_type, free_types, rows_per_frame, state, frame_rows):
         ctx.set_materialize_grads(False)
         loss, state_err, count, saved = _frame_losses_launch(net_out.detach(), target.detach(), node_type, free_types, rows_per_frame,
-                                                             state)
+                                                             state, frame_rows)
         ctx.cfg = saved + (count, net_out, target)
         out = _split_losses(loss, state_err, count)
         ctx.mark_non_differentiable(*(t for t in out[2:] if t is not None))
@@ -634,28 +693,34 @@ class _FrameLossesFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, g_frames, *unused):
-        x, tgt, nt, ldt, free_mask, per_frame, count, net_out, target = ctx.cfg
+        x, tgt, nt, ldt, free_mask, per_frame, ragged, count, net_out, target = ctx.cfg
         want_net, want_tgt = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if (g_loss is None and g_frames is None) or not (want_net or want_tgt):
-            return (None,) * 6
+            return (None,) * 7
         dev, (rows, F) = x.device, x.shape
-        B = rows // per_frame
+        B = ragged.B if ragged else rows // per_frame
         g = torch.cat([g_frames.to(dev).float().reshape(B) if g_frames is not None else _zeros(dev, B),
                        g_loss.to(dev).float().reshape(1) if g_loss is not None else _zeros(dev, 1)])
         d_net = torch.empty(rows, F, dtype=torch.float32, device=dev) if want_net else None
         d_tgt = torch.empty(rows, F, dtype=torch.float32, device=dev) if want_tgt else None
-        _lib.check(_lib.lib().hgn_frame_losses_bwd(
-            x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows, per_frame, count.data_ptr(),
-            g.data_ptr(), _ptr(d_net), _ld(d_net), _ptr(d_tgt), _ld(d_tgt), _lib.stream_ptr()), 'hgn_frame_losses_bwd')
-        return _like(d_net, net_out), _like(d_tgt, target), None, None, None, None
+        head = (x.data_ptr(), _ld(x), tgt.data_ptr(), _ld(tgt), F, nt.data_ptr(), ldt, free_mask, rows)
+        tail = (count.data_ptr(), g.data_ptr(), _ptr(d_net), _ld(d_net), _ptr(d_tgt), _ld(d_tgt), _lib.stream_ptr())
+        if ragged is not None:
+            _lib.check(_lib.lib().hgn_frame_losses_ragged_bwd(*head, ragged.host, ragged.ptr.data_ptr(), B, *tail),
+                       'hgn_frame_losses_ragged_bwd')
+        else:
+            _lib.check(_lib.lib().hgn_frame_losses_bwd(*head, per_frame, *tail), 'hgn_frame_losses_bwd')
+        return _like(d_net, net_out), _like(d_tgt, target), None, None, None, None, None
 
 
 def frame_losses(net_out: torch.Tensor, target: torch.Tensor, node_type: torch.Tensor, free_types, rows_per_frame=None,
-                 state=None) -> FrameLosses:
+                 state=None, frame_rows=None) -> FrameLosses:
     """The reference's masked MSE (flag.py:150-152: MSELoss()(target[mask], output[mask]), mask = the rows whose node type is listed
     in ``free_types``) per frame of a batch and over all rows, on the device, in two launches and without a host read
     (hgn_frame_losses).  ``net_out`` / ``target`` [rows, F] hold rows / rows_per_frame frames of ``rows_per_frame`` rows each (None:
-    one frame); views with a row stride are taken as they are.  ``state`` = (normalizer, cur, d, ca, prev, cp, state_target) adds the
+    one frame), or -- a ragged batch, frames of different meshes -- ``frame_rows`` = the row count of every frame in turn
+    (hgn_frame_losses_ragged: the same launches, order and bits per frame; giving both raises ValueError); views with a row stride are
+    taken as they are.  ``state`` = (normalizer, cur, d, ca, prev, cp, state_target) adds the
     error of the updated state ``ca*cur + normalizer.inverse(net_out)[:, :d] + cp*prev`` (``prev`` may be None; the bits of
     rollout_advance / the model's `update`) against ``state_target`` [rows, d]: what validation_step reports beside the loss.
     Sums are doubles in a fixed order (include/hgn_features.h): runs are bit-equal, and a frame's entries depend on its own rows
@@ -663,10 +728,12 @@ def frame_losses(net_out: torch.Tensor, target: torch.Tensor, node_type: torch.T
     -> FrameLosses(loss, per_frame [B], state_error, state_per_frame [B], count [B+1]).  When ``net_out`` or ``target`` requires grad
     the call is an autograd node: ``loss`` and ``per_frame`` are differentiable through ONE launch (hgn_frame_losses_bwd), the other
     outputs are not (the state error is an evaluation figure); an output nobody differentiates costs nothing in the backward pass."""
+    _one_split('frame_losses', rows_per_frame, frame_rows)
     _lib.require_gpu(net_out)
     if _needs_grad(net_out, target):
-        return FrameLosses(*_FrameLossesFn.apply(net_out, target, node_type, tuple(free_types), rows_per_frame, state))
-    loss, state_err, count, _ = _frame_losses_launch(net_out.detach(), target.detach(), node_type, free_types, rows_per_frame, state)
+        return FrameLosses(*_FrameLossesFn.apply(net_out, target, node_type, tuple(free_types), rows_per_frame, state, frame_rows))
+    loss, state_err, count, _ = _frame_losses_launch(net_out.detach(), target.detach(), node_type, free_types, rows_per_frame, state,
+                                                     frame_rows)
     return _split_losses(loss, state_err, count)
 
 
@@ -729,4 +796,40 @@ def radius_edges_batch(pos: torch.Tensor, node_type: torch.Tensor, n_graphs: int
     if total.value:
         _lib.check(L.hgn_radius_edges_batch_fill(*args, offsets.data_ptr(), s.data_ptr(), r.data_ptr(), _lib.stream_ptr()),
                    'hgn_radius_edges_batch_fill')
+    return s, r, graph_offsets
+
+
+def radius_edges_ragged(pos: torch.Tensor, node_type: torch.Tensor, frame_rows, radius: float, sender_type: int,
+                        receiver_type: int, nbr_rowptr=None, nbr=None):
+    """``radius_edges_batch`` for graphs of different sizes (hgn_radius_edges_ragged_count/_fill): ``pos`` / ``node_type`` hold the
+    rows of the disjoint union, graph b owns the ``frame_rows[b]`` rows after those of the graphs before it; no pair crosses a graph.
+    Every graph has its own mesh, so ``nbr_rowptr`` [rows+1] / ``nbr`` is the neighbour CSR of the UNION, in union ids (both None: no
+    exclusion).  Union ids in ascending (sender, receiver) order = the per-graph ``radius_edges`` results shifted by the rows before
+    the graph and concatenated.  One host read-back for the whole batch.
+    -> (senders, receivers) int64 and graph_offsets [B+1] int32 (edges before graph b; the last entry is the total)."""
+    _lib.require_gpu(pos)
+    dev = pos.device
+    pos = _f32_rows(pos)
+    rows = pos.shape[0]
+    nt, ldt = _type_column(node_type, dev, rows)
+    if nt.shape[0] != rows:
+        raise ValueError(f'radius_edges_ragged: {nt.shape[0]} node types for {rows} position rows')
+    ragged = _ragged(frame_rows, rows, dev, 'radius_edges_ragged')
+    L = _lib.lib()
+    nb = C.c_size_t(0)
+    _lib.check(L.hgn_radius_edges_ragged_workspace_bytes(rows, ragged.host, ragged.B, C.byref(nb)),
+               'hgn_radius_edges_ragged_workspace_bytes')
+    ws = _workspace(dev, nb.value, 'radius')
+    offsets = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    graph_offsets = torch.empty(ragged.B + 1, dtype=torch.int32, device=dev)
+    total = C.c_int64(0)
+    args = (pos.data_ptr(), _ld(pos), pos.shape[1], nt.data_ptr(), ldt, rows, ragged.host, ragged.ptr.data_ptr(), ragged.B,
+            float(radius), int(sender_type), int(receiver_type), _ptr(nbr_rowptr), _ptr(nbr))
+    _lib.check(L.hgn_radius_edges_ragged_count(*args, offsets.data_ptr(), graph_offsets.data_ptr(), C.byref(total),
+                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'hgn_radius_edges_ragged_count')
+    s = torch.empty(total.value, dtype=torch.int64, device=dev)
+    r = torch.empty(total.value, dtype=torch.int64, device=dev)
+    if total.value:
+        _lib.check(L.hgn_radius_edges_ragged_fill(*args, offsets.data_ptr(), s.data_ptr(), r.data_ptr(), _lib.stream_ptr()),
+                   'hgn_radius_edges_ragged_fill')
     return s, r, graph_offsets

@@ -70,6 +70,11 @@ class AbstractSystemModel(nn.Module):
     # unpickled from a checkpoint that lacks some of them starts with empty caches.
     _RUNTIME_CACHES = ('_fwd_cache', '_cells_key', '_cells_edges', '_batch_edges_key', '_batch_edges', '_nbr_key', '_nbr')
     _fwd_cache = _cells_key = _cells_edges = _batch_edges_key = _batch_edges = _nbr_key = _nbr = None
+    # The same kind of state for ragged batches (build_graph_frames): the edges of the last few meshes (`_frame_mesh_edges`) and of the
+    # last few unions of different meshes (`_frames_edges`); dropped from copies and pickles like the caches above.
+    _RAGGED_CACHES = ('_meshes', '_unions')
+    _meshes = _unions = None
+    _MESH_CACHE_SIZE, _UNION_CACHE_SIZE = 32, 8         # how many meshes / batch compositions a model keeps the edges of
 
     def __init__(self, params, node_size: int, edge_size: int, remote_edge_size: int = 7,
                  edge_sets=('mesh_edges',)) -> None:
@@ -117,7 +122,7 @@ class AbstractSystemModel(nn.Module):
         `_network` inside) and deep-copies it for evaluation.  Captured HIP graphs (the rollout replay cache) and the per-mesh
         edge caches are run-time state, not model state: a copy starts without them and captures again on its own device."""
         state = super().__getstate__()
-        state.update(dict.fromkeys(self._RUNTIME_CACHES))
+        state.update(dict.fromkeys(self._RUNTIME_CACHES + self._RAGGED_CACHES))
         return state
 
     def _select_architecture(self, connector):
@@ -144,6 +149,44 @@ class AbstractSystemModel(nn.Module):
             self._batch_edges_key = (n_graphs, num_nodes, senders)
         return self._batch_edges
 
+    def _frame_mesh_edges(self, cells: Tensor, deform: bool = False):
+        """`_mesh_edges` for batches that mix meshes: the same key (the ``cells`` tensor itself, else equal content) over the last
+        `_MESH_CACHE_SIZE` meshes instead of the last one."""
+        if self._meshes is None:
+            self._meshes = []
+        for key, edges in self._meshes:
+            if key is cells:
+                return edges
+        for key, edges in self._meshes:
+            if key.shape == cells.shape and key.device == cells.device and torch.equal(key, cells):
+                return edges
+        s, r, _ = features.cells_to_edges(cells.to(device), deform)
+        edges = (s.contiguous(), r.contiguous())
+        self._meshes = self._meshes[-(self._MESH_CACHE_SIZE - 1):] + [(cells, edges)]
+        return edges
+
+    def _frames_edges(self, cells, frame_rows: Tuple[int, ...], deform: bool = False):
+        """Mesh edges of the disjoint union of frames of DIFFERENT meshes: ``cells[b]`` is the mesh of frame b, whose ids are shifted
+        by the rows of the frames before it (what batching.batch_graphs does), graph-major.  Built once per batch composition -- the
+        same meshes (`_frame_mesh_edges`) with the same row counts in the same order -- and then handed out as the same tensors, so the
+        topology cache and the captured forward of a rollout see one topology."""
+        if len(cells) != len(frame_rows):
+            raise ValueError(f'{len(cells)} meshes for {len(frame_rows)} frames')
+        meshes = [self._frame_mesh_edges(c, deform) for c in cells]
+        if self._unions is None:
+            self._unions = []
+        for rows, held, union in self._unions:
+            if rows == frame_rows and all(a[0] is b[0] for a, b in zip(held, meshes)):
+                return union
+        first, senders, receivers = 0, [], []
+        for (s, r), n in zip(meshes, frame_rows):
+            senders.append(s + first)
+            receivers.append(r + first)
+            first += n
+        union = (torch.cat(senders).contiguous(), torch.cat(receivers).contiguous())
+        self._unions = self._unions[-(self._UNION_CACHE_SIZE - 1):] + [(frame_rows, meshes, union)]
+        return union
+
     @staticmethod
     def _union_rows(inputs: Dict, name: str, n_graphs: int, num_nodes: int) -> Tensor:
         """``inputs[name]`` as the [B*N, .] rows of the union: a [B, N, .] series is flattened, a shared [N, .] entry (one mesh for
@@ -153,11 +196,19 @@ class AbstractSystemModel(nn.Module):
             t = t.unsqueeze(0).expand(n_graphs, num_nodes, -1)
         return t.reshape(n_graphs * num_nodes, -1).contiguous()
 
-    def _frame_rows(self, inputs: Dict, names, batched: bool):
-        """What the one body behind build_graph and build_graph_batch works on: -> (rows, B, N), the series ``names`` and
-        `mesh_pos` on the device.  A single frame: as they are, B is None.  A batch: [B, N, .] flattened to the [B*N, .] rows of the
-        union (views: no launch), a shared `mesh_pos` repeated (`_union_rows`: the one copy a batch adds)."""
+    def _frame_rows(self, inputs: Dict, names, batched: bool, frame_rows=None):
+        """What the one body behind build_graph, build_graph_batch and build_graph_frames works on: -> (rows, B, N), the series
+        ``names`` and `mesh_pos` on the device.  A single frame: as they are, B is None.  A batch: [B, N, .] flattened to the [B*N, .]
+        rows of the union (views: no launch), a shared `mesh_pos` repeated (`_union_rows`: the one copy a batch adds).  A ragged batch
+        (``frame_rows`` given; ``inputs`` is what `concat_frames` returns): the rows as they are, B is the tuple ``frame_rows`` and N
+        the number of rows of the union."""
         rows = {name: inputs[name].to(device) for name in names}
+        if frame_rows is not None:
+            rows['mesh_pos'] = inputs['mesh_pos'].to(device)
+            total = rows['node_type'].shape[0]
+            if sum(frame_rows) != total or any(t.shape[0] != total for t in rows.values()):
+                raise ValueError(f'frames of {frame_rows} rows do not add up to the {total} rows given')
+            return rows, tuple(frame_rows), total
         if not batched:
             rows['mesh_pos'] = inputs['mesh_pos'].to(device)
             return rows, None, rows['node_type'].shape[0]
@@ -167,7 +218,12 @@ class AbstractSystemModel(nn.Module):
         return rows, B, N
 
     def _frame_edges(self, cells: Tensor, B, N: int, deform: bool = False):
-        """-> ((senders, receivers) of the frame, or of the union of B frames when B is not None; those of the one mesh)."""
+        """-> ((senders, receivers) of the frame, or of the union of B frames when B is not None; those of the one mesh).  A ragged
+        batch (B a tuple of row counts, ``cells`` the meshes of its frames): the union of the different meshes, twice -- the union is
+        the one mesh there is."""
+        if isinstance(B, tuple):
+            union = self._frames_edges(cells, B, deform)
+            return union, union
         mesh = self._mesh_edges(cells, deform)
         return (mesh if B is None else self._union_mesh_edges(*mesh, B, N)), mesh
 
@@ -181,6 +237,50 @@ class AbstractSystemModel(nn.Module):
         B, N = inputs['node_type'].shape[0], inputs['node_type'].shape[1]
         return {name: (t.reshape(B * N, -1) if name != 'cells' and torch.is_tensor(t) and t.dim() == 3 and tuple(t.shape[:2]) == (B, N)
                        else t) for name, t in inputs.items()}
+
+    @staticmethod
+    def concat_frames(frames) -> Tuple[Dict, Tuple[int, ...]]:
+        """B frames of DIFFERENT meshes (a ragged batch) -> (flat, frame_rows): every per-node series [N_b, .] is concatenated to the
+        [rows, .] rows of the disjoint union (frame b owns the N_b rows after those of the frames before it, the row order of
+        build_graph_frames), `flat['cells']` is the list of the frames' `cells` (the same objects), and ``frame_rows`` = (N_0, ..,
+        N_{B-1}) is read from `node_type`.  training_step, validation_step, get_target, update and the loss mask are element-wise over
+        rows, so they take ``flat`` together with the graph of build_graph_frames / expand_graph_frames unchanged."""
+        frames = list(frames)
+        if not frames:
+            raise ValueError('concat_frames: no frame')
+        flat = {name: torch.cat([frame[name] for frame in frames]) for name in frames[0] if name != 'cells'}
+        flat['cells'] = [frame['cells'] for frame in frames]
+        return flat, tuple(int(frame['node_type'].shape[0]) for frame in frames)
+
+    def build_graph_frames(self, frames, is_training: bool) -> MultiGraphWithPos:
+        """Not in the reference (which builds one graph per frame and concatenates them with MeshSimulator._get_batched): B frames of
+        DIFFERENT meshes -- a sequence of the dicts build_graph takes, e.g. frames of different trajectories of cylinder_flow or
+        deforming_plate -- become the disjoint union of B graphs through the body build_graph and build_graph_batch run, in the handful
+        of launches a single frame takes.  Node ids of frame b are shifted by the rows of the frames before it, as
+        batching.batch_graphs does, and every edge set is graph-major: ids and features are those of the per-frame build_graph
+        results concatenated.  Mesh edges are computed once per distinct mesh (the last `_MESH_CACHE_SIZE` are kept), the union's index
+        tensors once per batch composition, so repeated calls hand the topology cache the same tensors; the plate's `world_edges` come
+        from ONE features.radius_edges_ragged query over the neighbour CSR of the union.  A pair (`concat_frames` result, its
+        ``frame_rows``) is taken in place of the sequence.  Gradients: the rules of build_graph_batch (`position_gradients` for the
+        plate).
+        Semantic difference to B separate build_graph calls, the one build_graph_batch documents: each normaliser accumulates ONCE,
+        with the statistics of the whole batch."""
+        if isinstance(frames, tuple) and len(frames) == 2 and isinstance(frames[0], dict):
+            flat, frame_rows = frames
+        else:
+            flat, frame_rows = self.concat_frames(frames)
+        return self._build(flat, is_training, batched=True, frame_rows=tuple(int(n) for n in frame_rows))
+
+    def expand_graph_frames(self, graph: MultiGraphWithPos, frame_rows, step: int, num_steps: int, is_training: bool) -> MultiGraph:
+        """``expand_graph_batch`` for the union build_graph_frames returns: without a connector and without a graph balancer the
+        union comes back as a MultiGraph.  Out of scope: either stage on a ragged batch (HgnError) -- clusters and balance edges are
+        per mesh, and batching.batch_graphs joins graphs of one size only: such frames take the per-frame route, build_graph and
+        expand_graph on every frame, one graph per network call."""
+        if self._balancer or self._rmp:
+            raise _lib.HgnError('expand_graph_frames: remote message passing (connector) and the graph balancer have no form for a batch '
+                                'of different meshes; take the per-frame route (build_graph and expand_graph on the frames one by one, '
+                                'one graph per network call), or configure the model without these stages')
+        return MultiGraph(node_features=graph.node_features, edge_sets=graph.edge_sets)
 
     @staticmethod
     def _refresh_due(step: int, num_steps: int, frequency) -> bool:
@@ -224,7 +324,8 @@ class AbstractSystemModel(nn.Module):
         its edges graph by graph -- ids and order of batch_graphs over the per-frame expand_graph results.
         Semantic difference to B expand_graph calls: each normaliser accumulates ONCE, with the statistics of the whole batch, and
         `hyper_noise` is drawn once per call for all B*K hyper nodes.
-        Out of scope: a configured graph balancer (HgnError) and meshes that differ within one batch.  Like expand_graph, a
+        Out of scope: a configured graph balancer (HgnError); meshes that differ within one batch go through build_graph_frames /
+        expand_graph_frames, which take no connector.  Like expand_graph, a
         connector refuses a graph that carries position gradients unless `position_gradients` is set."""
         if self._balancer:
             raise _lib.HgnError('expand_graph_batch: the graph balancer stage has no batched form; expand the frames one by one with '
@@ -280,21 +381,31 @@ class AbstractSystemModel(nn.Module):
         target_normalized = self.get_target(data_frame)
         return self._training_loss(target_normalized, network_output, data_frame)
 
-    def training_step_batch(self, graph, data_frame, n_graphs: int) -> Tuple[Tensor, Tensor]:
+    def training_step_batch(self, graph, data_frame, n_graphs) -> Tuple[Tensor, Tensor]:
         """Not in the reference, whose batched training step returns one scalar while it logs a loss per trajectory
         (MeshSimulator.py:151-156): `training_step` for the union graph of ``n_graphs`` frames (build_graph_batch /
         expand_graph_batch) and the flattened frames (`flatten_frames`), always through features.frame_losses.
         -> (loss over all rows, the loss of every frame [B] detached).  ``loss`` is what `training_step` returns with `loss_kernel =
         True`: the same squares summed in double, grouped by frame here and by 256 rows there, and rounded to fp32 once -- equal
-        bits unless the two double sums fall on either side of an fp32 rounding boundary."""
+        bits unless the two double sums fall on either side of an fp32 rounding boundary.
+        ``n_graphs`` may be a sequence of per-frame row counts instead: the union of a ragged batch (build_graph_frames /
+        expand_graph_frames) with the frames of `concat_frames` and its ``frame_rows``."""
         network_output = self(graph)
         target_normalized = self.get_target(data_frame)
-        rows = network_output.shape[0]
-        if int(n_graphs) < 1 or rows % int(n_graphs):
-            raise ValueError(f'training_step_batch: {rows} rows do not split into {n_graphs} frames')
+        rows_per_frame, ragged = self._frame_split('training_step_batch', network_output.shape[0], n_graphs)
         res = features.frame_losses(network_output, target_normalized, data_frame['node_type'], self._LOCKSTEP.free_types,
-                                    rows // int(n_graphs))
+                                    rows_per_frame, **ragged)
         return res.loss, res.per_frame.detach()
+
+    @staticmethod
+    def _frame_split(what: str, rows: int, n_graphs):
+        """The third argument of the batched steps as features.frame_losses takes it -> (rows_per_frame, further keywords): an int B
+        = frames of rows / B rows each; a sequence = the row count of every frame of a ragged batch (`frame_rows`)."""
+        if isinstance(n_graphs, (tuple, list)):
+            return None, {'frame_rows': tuple(int(n) for n in n_graphs)}
+        if int(n_graphs) < 1 or rows % int(n_graphs):
+            raise ValueError(f'{what}: {rows} rows do not split into {n_graphs} frames')
+        return rows // int(n_graphs), {}
 
     @torch.no_grad()
     def validation_step(self, graph: MultiGraph, data_frame: Dict) -> Tuple[Tensor, Tensor]:
@@ -309,21 +420,20 @@ class AbstractSystemModel(nn.Module):
         return loss, state_error
 
     @torch.no_grad()
-    def validation_step_batch(self, graph: MultiGraph, data_frame: Dict, n_graphs: int) -> Tuple[Tensor, Tensor]:
+    def validation_step_batch(self, graph: MultiGraph, data_frame: Dict, n_graphs) -> Tuple[Tensor, Tensor]:
         """Not in the reference, which validates one frame per call (MeshSimulator.py:295-297): `validation_step` for the union graph
         of ``n_graphs`` frames (build_graph_batch / expand_graph_batch) and the flattened frames (`flatten_frames`).
         -> (loss [B], state_error [B]): float32 device tensors, entry b = what `validation_step` returns for frame b; no host read.
         The network, `get_target(flat, False)` and ONE features.frame_losses call, which forms the updated state with the constants
-        of `_LOCKSTEP` (the bits of `update`) and compares it against the `_LOCKSTEP.target` series on the free rows."""
+        of `_LOCKSTEP` (the bits of `update`) and compares it against the `_LOCKSTEP.target` series on the free rows.
+        ``n_graphs`` may be a sequence of per-frame row counts instead (a ragged batch: build_graph_frames, `concat_frames`)."""
         ls = self._LOCKSTEP
         prediction = self(graph)
         target_normalized = self.get_target(data_frame, False)
-        rows = prediction.shape[0]
-        if int(n_graphs) < 1 or rows % int(n_graphs):
-            raise ValueError(f'validation_step_batch: {rows} rows do not split into {n_graphs} frames')
-        res = features.frame_losses(prediction, target_normalized, data_frame['node_type'], ls.free_types, rows // int(n_graphs),
+        rows_per_frame, ragged = self._frame_split('validation_step_batch', prediction.shape[0], n_graphs)
+        res = features.frame_losses(prediction, target_normalized, data_frame['node_type'], ls.free_types, rows_per_frame,
                                     state=(self._output_normalizer, data_frame[ls.state], ls.d, ls.ca,
-                                           data_frame[ls.prev] if ls.prev else None, ls.cp, data_frame[ls.target]))
+                                           data_frame[ls.prev] if ls.prev else None, ls.cp, data_frame[ls.target]), **ragged)
         return res.per_frame, res.state_per_frame
 
     @torch.no_grad()
@@ -442,6 +552,61 @@ class AbstractSystemModel(nn.Module):
         return (self._rollout_result(windows, node_type, slab.transpose(0, 1), **{k: v.transpose(0, 1) for k, v in records.items()}),
                 self._batch_errors(windows, ls.errors, slab))
 
+    @torch.no_grad()
+    def rollout_frames(self, trajectories, num_steps: int):
+        """Not in the reference: `rollout` for R trajectories of DIFFERENT meshes in lock step.  ``trajectories`` is a sequence of the
+        dicts `rollout` takes ([T, N_r, .] series, `cells` and `mesh_pos` per frame), all with at least ``num_steps`` frames (None: the
+        frames of the first one).  Every step is one union build over the R current states (the body of build_graph_frames on the
+        concatenated rows, is_training=False; for the plate one radius query for all trajectories), expand_graph_frames, the network,
+        and ONE features.rollout_advance launch over all rows with the constants of `_LOCKSTEP`, which writes the new state, the
+        recorded row and the model's extra records straight into their slices of [steps, rows, .] slabs.  The meshes and node types are
+        those of every trajectory's frame 0, as in `rollout`, so every step sees one batch composition and the same index tensors.
+        -> a list, per trajectory (result, errors [steps]): what `rollout` returns for it (the recorded series are views of the slabs).
+        Out of scope: a connector or a graph balancer (expand_graph_frames raises)."""
+        ls = self._LOCKSTEP
+        series = [{name: torch.squeeze(t, 0) for name, t in trajectory.items()} for trajectory in trajectories]
+        if not series:
+            return []
+        if num_steps is None:
+            num_steps = series[0][ls.state].shape[0]
+        if any(t[name].shape[0] < num_steps for t in series for name in (ls.state,) + ((ls.fallback,) if ls.fallback else ())):
+            raise ValueError(f'rollout_frames: every trajectory needs {num_steps} frames to advance in lock step')
+        starts = [self._first_frame(trajectory) for trajectory in trajectories]
+        flat, frame_rows = self.concat_frames(starts)                   # fresh memory: the state buffers are written, the trajectories are not
+        total = sum(frame_rows)
+        cur = flat[ls.state].float().contiguous()
+        prev = flat[ls.prev].float().contiguous() if ls.prev else None
+        node_type = flat['node_type'].to(torch.int64)
+        scripted = None
+        if ls.fallback:                                                 # [steps, rows, d], concatenated once
+            scripted = torch.cat([t[ls.fallback][:num_steps].to(device) for t in series], dim=1).float().contiguous()
+        slab = torch.empty(num_steps, total, ls.d, dtype=torch.float32, device=cur.device)
+        records = self._rollout_records(lambda width: torch.empty(num_steps, total, width, dtype=torch.float32, device=cur.device))
+        nxt, prev_nxt = torch.empty_like(cur), (torch.empty_like(prev) if ls.prev else None)
+        frame = {'cells': flat['cells'], 'mesh_pos': flat['mesh_pos'], 'node_type': node_type}
+        for step in range(num_steps):
+            frame[ls.state] = cur
+            if ls.prev:
+                frame[ls.prev] = prev
+            if ls.fallback:
+                frame[ls.fallback] = scripted[step]
+            graph = self.expand_graph_frames(self.build_graph_frames((frame, frame_rows), is_training=False), frame_rows, step,
+                                             ls.expand_steps or num_steps, is_training=False)
+            outputs = {name: record[step] for name, record in records.items()}
+            if ls.prev:
+                outputs['prev_out'] = prev_nxt                          # the old state goes into the swap buffer
+            features.rollout_advance(self(graph), self._output_normalizer, cur, ls.d, ls.ca, prev, ls.cp, node_type, ls.free_types,
+                                     scripted[step] if ls.fallback else None, nxt, rec=slab[step], rec_before=ls.record_before,
+                                     inv_from=ls.inv_from or 0, **outputs)
+            cur, nxt, prev, prev_nxt = nxt, cur, prev_nxt, prev
+        results, first = [], 0
+        for trajectory, t, start, n in zip(trajectories, series, starts, frame_rows):
+            own = slice(first, first + n)
+            result = self._rollout_result(trajectory, start['node_type'], slab[:, own], **{k: v[:, own] for k, v in records.items()})
+            results.append((result, self._per_step_mse(t[ls.errors][:num_steps].to(device), slab[:, own])))
+            first += n
+        return results
+
     def _rollout_records(self, empty) -> Dict[str, Tensor]:
         """The slabs a model records beside the state, by the rollout_advance output that fills them; ``empty(width)`` makes one."""
         return {}
@@ -462,7 +627,7 @@ class AbstractSystemModel(nn.Module):
     # ---- seeded training noise: one launch for a batch of frames --------------------------------------------------------
     noise_seed = None       # the seed `add_noise` uses when the call gives none; a plain value (it travels in pickles, old ones read None)
 
-    def add_noise(self, frames: Dict[str, Tensor], draw: int, frame_ids=None, seed=None) -> Dict[str, Tensor]:
+    def add_noise(self, frames: Dict[str, Tensor], draw: int, frame_ids=None, seed=None, frame_rows=None) -> Dict[str, Tensor]:
         """The reference's training noise (src/data/preprocessing.py:84-98, once per frame) for one frame ([N, .] series) or for
         stacked frames ([B, N, .], what build_graph_batch takes) in ONE features.add_noise launch: normal(0, `noise`) on the NORMAL
         rows of ``frames[field]``, and (1 - `gamma`) times the same sample on ``frames['target|' + field]``; `field`, `noise` and
@@ -471,6 +636,8 @@ class AbstractSystemModel(nn.Module):
         The sample of a row depends on (``seed``, ``draw``, the frame's id, the node) alone: ``seed`` defaults to `self.noise_seed`
         (ValueError if both are None), ``draw`` counts the draws (the training step, say) and frame b has id ``frame_ids[b]``,
         default b.  A rank of a data-parallel run that passes the global ids of its frames gets the samples a single process gets.
+        ``frame_rows`` (a sequence of row counts): ``frames`` is the ``flat`` of `concat_frames`, a ragged batch whose frame b has
+        ``frame_rows[b]`` rows; still one launch, and every frame gets the samples it gets on its own with its id.
         -> a shallow copy of ``frames`` with `field` and `target|field` replaced by fresh tensors in the input's shape; every other
         entry is the same object (the flag's `prev|world_pos` is untouched, as in the reference) and the inputs are not written.  A
         scale of 0, or a `model` section without `noise`, returns the copy without a launch.
@@ -487,10 +654,10 @@ class AbstractSystemModel(nn.Module):
             raise ValueError('add_noise: no seed (pass `seed`, or set `model.noise_seed`)')
         field = self._params.get('field')
         x, target = frames[field].to(device), frames['target|' + field].to(device)
-        rows_per_frame = x.shape[-2]
+        rows_per_frame = x.shape[-2] if frame_rows is None else None
         noisy, noisy_target = features.add_noise(
             x.reshape(-1, x.shape[-1]), frames['node_type'].to(device).reshape(-1, 1), (NodeType.NORMAL.value,), float(scale), seed,
-            draw, target.reshape(-1, target.shape[-1]), 1.0 - float(self._params.get('gamma')), rows_per_frame, frame_ids)
+            draw, target.reshape(-1, target.shape[-1]), 1.0 - float(self._params.get('gamma')), rows_per_frame, frame_ids, frame_rows)
         out[field], out['target|' + field] = noisy.reshape(x.shape), noisy_target.reshape(target.shape)
         return out
 
@@ -620,8 +787,8 @@ class FlagModel(AbstractSystemModel):
         whole batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
         return self._build(inputs, is_training, batched=True)
 
-    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
-        rows, B, N = self._frame_rows(inputs, ('world_pos', 'prev|world_pos', 'node_type'), batched)
+    def _build(self, inputs: Dict, is_training: bool, batched: bool, frame_rows=None) -> MultiGraphWithPos:
+        rows, B, N = self._frame_rows(inputs, ('world_pos', 'prev|world_pos', 'node_type'), batched, frame_rows)
         world_pos, mesh_pos = rows['world_pos'], rows['mesh_pos']
         # velocity (3) | one-hot(type != NORMAL) (2)                                              flag.py:68-74
         node_features = features.node_features(world_pos, rows['prev|world_pos'], rows['node_type'], self._TYPE_MAP, 2)
@@ -710,8 +877,8 @@ class CylinderModel(AbstractSystemModel):
         batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
         return self._build(inputs, is_training, batched=True)
 
-    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
-        rows, B, N = self._frame_rows(inputs, ('velocity', 'node_type'), batched)
+    def _build(self, inputs: Dict, is_training: bool, batched: bool, frame_rows=None) -> MultiGraphWithPos:
+        rows, B, N = self._frame_rows(inputs, ('velocity', 'node_type'), batched, frame_rows)
         velocity, mesh_pos = rows['velocity'], rows['mesh_pos']
         node_features = features.node_features(velocity, None, rows['node_type'], self._TYPE_MAP, 4)
         (senders, receivers), _ = self._frame_edges(inputs['cells'], B, N)
@@ -754,6 +921,11 @@ class CylinderModel(AbstractSystemModel):
         (cylinder.py:178); the NORMAL and OUTFLOW nodes are integrated, the state AFTER the step and the predicted pressure are
         recorded.  -> `pred_velocity` [W, T, N, 2], `pred_pressure` [W, T, N, 1], errors [W, T]."""
         return super().rollout_batch(windows, None)
+
+    def rollout_frames(self, trajectories, num_steps: int):
+        """The lock-step rollout of the base class for trajectories of different meshes.  Like `rollout`, it runs the whole length of
+        the trajectories whatever `num_steps` says (cylinder.py:178): the length of the first one, which the others must reach."""
+        return super().rollout_frames(trajectories, None)
 
     def _rollout_records(self, empty):
         return {'inv_out': empty(1)}                                      # the pressure column of the output
@@ -809,20 +981,24 @@ class PlateModel(AbstractSystemModel):
         batch (same running sums and counts afterwards, `num_accumulations` grows by 1 instead of B)."""
         return self._build(inputs, is_training, batched=True)
 
-    def _build(self, inputs: Dict, is_training: bool, batched: bool) -> MultiGraphWithPos:
+    def _build(self, inputs: Dict, is_training: bool, batched: bool, frame_rows=None) -> MultiGraphWithPos:
         if not self.position_gradients and _carries_grad(inputs['world_pos'], inputs['mesh_pos'], inputs['target|world_pos']):
-            raise _lib.HgnError(f"PlateModel.{'build_graph_batch' if batched else 'build_graph'} is not differentiable with respect to "
+            method = 'build_graph_frames' if frame_rows else 'build_graph_batch' if batched else 'build_graph'
+            raise _lib.HgnError(f'PlateModel.{method} is not differentiable with respect to '
                                 'positions (its world edges are a radius query of world_pos); pass tensors that do not require grad, '
                                 'or call it under torch.no_grad(), or set `model.position_gradients = True` (which pairs are world '
                                 'edges is then a constant)')
-        rows, B, N = self._frame_rows(inputs, ('world_pos', 'target|world_pos', 'node_type'), batched)
+        rows, B, N = self._frame_rows(inputs, ('world_pos', 'target|world_pos', 'node_type'), batched, frame_rows)
         world_pos, mesh_pos, node_type = rows['world_pos'], rows['mesh_pos'], rows['node_type']
         (senders, receivers), mesh = self._frame_edges(inputs['cells'], B, N, deform=True)
         # world edges: obstacle -> normal pairs closer than the radius that are not mesh edges (excluded through the neighbour CSR of
-        # the ONE mesh, on local ids); a batch takes all its frames in one query                          plate.py:84-110
+        # the ONE mesh, on local ids; a ragged batch: of the union, on union ids); a batch takes all its frames in one query
+        #                                                                                                plate.py:84-110
         nbr_rowptr = self._mesh_neighbours(*mesh, N, world_pos.device)
         query = (self._RADIUS, NodeType.OBSTACLE.value, NodeType.NORMAL.value, nbr_rowptr, self._nbr)
-        if batched:
+        if frame_rows is not None:
+            world_senders, world_receivers, _ = features.radius_edges_ragged(_value(world_pos), node_type, B, *query)
+        elif batched:
             world_senders, world_receivers, _ = features.radius_edges_batch(_value(world_pos), node_type, B, *query)
         else:
             world_senders, world_receivers = features.radius_edges(_value(world_pos), node_type, *query)
@@ -893,7 +1069,7 @@ class PlateModel(AbstractSystemModel):
         cells = windows['cells']
         triangles = torch.cat((cells[..., 0:3], cells[..., [2, 3, 0]]), dim=-2)                         # plate.py:289-297
         return {'faces': triangles, 'mesh_pos': windows['mesh_pos'],
-                'mask': torch.eq(node_type[:, :, 0], NodeType.OBSTACLE.value), 'gt_pos': windows['world_pos'],
+                'mask': torch.eq(node_type[..., 0], NodeType.OBSTACLE.value), 'gt_pos': windows['world_pos'],
                 'pred_pos': pred_pos, 'cur_positions': prev_out, 'cur_velocities': inv_out}
 
     @torch.no_grad()

@@ -24,6 +24,8 @@
  *   data/preprocessing.py:84-98      Preprocessing._add_noise, per frame         -> hgn_training_noise (a batch of frames)
  *   model/flag.py:146-167, cylinder.py:123-153, plate.py:218-244
  *                                    the masked MSE of training / validation_step -> hgn_frame_losses (per frame of a batch), _bwd
+ *   the three batch entries above for frames of different meshes (a ragged batch) -> hgn_radius_edges_ragged_count/_fill,
+ *                                    hgn_training_noise_ragged, hgn_frame_losses_ragged, _ragged_bwd
  */
 #ifndef HGN_FEATURES_H
 #define HGN_FEATURES_H
@@ -322,6 +324,88 @@ int hgn_frame_losses_bwd(const float* net_out, int64_t ld_out, const float* targ
                          int64_t ldt, uint32_t free_mask, int64_t rows, int64_t rows_per_frame, const int64_t* count,
                          const float* g /* nullable */, float* d_net, int64_t ld_dnet, float* d_target, int64_t ld_dtgt,
                          void* stream);
+
+/* ==== ragged batches: frames of different meshes in one batch ===================================================================
+ * cylinder_flow and deforming_plate give every trajectory its own mesh, so a batch that mixes trajectories has frames of different
+ * sizes.  A ragged batch is B frames of frame_rows = (N_0, .., N_{B-1}) rows, every N_b >= 1, rows = sum N_b; frame b owns the union
+ * rows [P_b, P_{b+1}), P the exclusive prefix of frame_rows.  Every entry below takes the batch twice:
+ *   frame_rows  HOST   const int64_t [B]     validated before any launch
+ *   frame_ptr   DEVICE const int32_t [B+1]   = P, the caller's contract (built once per distinct batch shape and kept)
+ * HGN_E_INVALID with the entry's name, before any launch: B < 1, an entry < 1, a sum that differs from rows (so rows = 0 is refused:
+ * there is no empty ragged batch), rows >= 2^31, null frame_rows or frame_ptr, and whatever the uniform entry refuses.
+ * The kernels clamp every bound they read from frame_ptr to [0, rows] and search it for a frame in [0, B): a frame_ptr that is not
+ * the prefix of frame_rows gives wrong figures, never a read or write outside the caller's buffers.
+ * Plain vector loads and stores, no atomics, equal bits on every run, 256 threads per workgroup, as the uniform kernels. */
+
+/* ---- world edges of a ragged batch (plate.py:84-110 once per frame, MeshSimulator.py:159-234 for the union) ----------------------
+ * hgn_radius_edges_batch_* for graphs of different sizes: pos / node_type hold the rows of the union, graph b owns rows
+ * [P_b, P_{b+1}), a pair (s, r) is reported only if both ends lie in the same graph.  Every graph has its own mesh: nbr_rowptr
+ * [rows+1] / nbr is the neighbour CSR of the UNION, rows and entries in union ids (both null = no exclusion).  Types, radius and the
+ * distance expression are those of hgn_radius_edges_count.  Output: union ids in ascending (s, r) order = the concatenation over b of
+ * what hgn_radius_edges_count/_fill return for graph b alone, shifted by P_b.
+ * _count fills offsets [rows+1] (device int32, exclusive prefix of the per-sender counts, offsets[rows] = total) and, when
+ * graph_offsets is not NULL, graph_offsets [B+1] (device int32: graph_offsets[b] = offsets[P_b] = edges before graph b,
+ * graph_offsets[B] = total), and returns the total on the HOST: ONE stream synchronisation for the batch.  _fill writes senders /
+ * receivers [total] int64.  One wavefront per sender row finds its graph by bisection of frame_ptr and sweeps the receivers of that
+ * graph in chunks of 64: sum_b N_b^2 / 64 chunk iterations; sender rows of another type leave at once.
+ * HGN_E_INVALID: the ragged refusals above with rows > 0x7ffffffe, whatever hgn_radius_edges_count refuses (d outside 1..3, ld < d,
+ * ldt < 1, radius not >= 0, null pos / node_type, only one of nbr_rowptr / nbr), null outputs, workspace too small. */
+int hgn_radius_edges_ragged_workspace_bytes(int64_t rows, const int64_t* frame_rows /*host [B]*/, int64_t n_graphs, size_t* bytes);
+int hgn_radius_edges_ragged_count(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt, int64_t rows,
+                                  const int64_t* frame_rows /*host [B]*/, const int32_t* frame_ptr /*device [B+1]*/,
+                                  int64_t n_graphs, float radius, int sender_type, int receiver_type, const int32_t* nbr_rowptr,
+                                  const int32_t* nbr, int32_t* offsets /*[rows+1]*/, int32_t* graph_offsets /*[B+1] nullable*/,
+                                  int64_t* total /*host*/, void* workspace, size_t ws_bytes, void* stream);
+int hgn_radius_edges_ragged_fill(const float* pos, int64_t ld, int d, const int64_t* node_type, int64_t ldt, int64_t rows,
+                                 const int64_t* frame_rows /*host [B]*/, const int32_t* frame_ptr /*device [B+1]*/,
+                                 int64_t n_graphs, float radius, int sender_type, int receiver_type, const int32_t* nbr_rowptr,
+                                 const int32_t* nbr, const int32_t* offsets, int64_t* senders, int64_t* receivers, void* stream);
+
+/* ---- seeded training noise for a ragged batch (src/data/preprocessing.py:84-98, Preprocessing._add_noise) -------------------------
+ * hgn_training_noise with row r -> (f, n = r - P_f) found by bisection of frame_ptr, fid = frame_ids ? (uint32)frame_ids[f] :
+ * (uint32)f.  The same Philox4x32-10 counter (n, fid, draw lo, draw hi), key and Box-Muller, the same free-row rule and arithmetic:
+ * a row's sample stays a function of (seed, draw, frame id, node) alone, so the rows of frame f have the bits hgn_training_noise gives
+ * that frame on its own with frame id fid.  ONE launch, one thread per row.
+ * HGN_E_INVALID before any launch: the ragged refusals above and whatever hgn_training_noise refuses (d outside 1..4, a row stride
+ * smaller than d, ldt < 1, std_ negative or not finite, target and out_target not both null or both given, null x / node_type /
+ * out_x). */
+int hgn_training_noise_ragged(const float* x, int64_t ldx, int d, const int64_t* node_type, int64_t ldt, uint32_t free_mask,
+                              int64_t rows, const int64_t* frame_rows /*host [B]*/, const int32_t* frame_ptr /*device [B+1]*/,
+                              int64_t n_frames, const int64_t* frame_ids /* nullable */, uint64_t seed, uint64_t draw, float std_,
+                              const float* target /* nullable */, int64_t ld_tgt, float target_scale, float* out_x, int64_t ld_ox,
+                              float* out_target /* null iff target is */, int64_t ld_ot, void* stream);
+
+/* ---- per-frame losses of a ragged batch (flag.py:146-167, cylinder.py:123-153, plate.py:218-244: training_step and
+ * validation_step; algorithms/MeshSimulator.py:151-156 "loss per trajectory", :295-297 [loss, pos_error] per frame) --------------
+ * The outputs, formulas and NaN rule of hgn_frame_losses / _bwd with frame f = rows [P_f, P_{f+1}).  The order is the documented one:
+ * chunks of HGN_LOSS_CHUNK_ROWS rows counted from the frame's own first row, lanes by halving strides, the four wavefronts as
+ * (0 + 1) + (2 + 3), chunks ascending, frames ascending for entry B.  Hence
+ *   - entries f < B have the bits that hgn_frame_losses gives for that frame alone;
+ *   - with all N_b equal, all B+1 entries and the whole backward have the bits of the uniform entries.
+ * Forward: at most two launches, nothing is read on the host.  The partial pass is a grid of B x ceil(max N_b / HGN_LOSS_CHUNK_ROWS)
+ * workgroups -- workgroup (f, k) takes chunk k of frame f and leaves at once when the frame has no such chunk -- and one workgroup
+ * finalises, adding for every frame the chunks it has.  The workspace holds one partial triple per workgroup of that grid
+ * (hgn_frame_losses_ragged_workspace_bytes: grows with B and with max N_b; 8-byte aligned).
+ * Backward: ONE launch, flat over [rows, F]; the frame of a row by bisection of frame_ptr; count [B+1] is the forward's, g [B+1] as in
+ * hgn_frame_losses_bwd.
+ * HGN_E_INVALID before any launch: the ragged refusals above, a grid of B x chunks that does not fit one launch (>= 2^31 workgroups),
+ * and whatever hgn_frame_losses / _bwd refuse (F outside 1..HGN_MAX_FEATURE_WIDTH, a state part given in part, state_err null with a
+ * state part or given without one, d outside 1..F with a state part, a row stride smaller than its row, ldt < 1, no output asked for,
+ * null net_out / target / node_type / loss / count, a workspace that is null, misaligned or too small). */
+int hgn_frame_losses_ragged_workspace_bytes(int64_t rows, const int64_t* frame_rows /*host [B]*/, int64_t n_frames, size_t* bytes);
+int hgn_frame_losses_ragged(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                            const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows,
+                            const int64_t* frame_rows /*host [B]*/, const int32_t* frame_ptr /*device [B+1]*/, int64_t n_frames,
+                            const float* acc_sum, const float* acc_sumsq, const float* acc_count, float eps, const float* cur,
+                            int64_t ld_cur, int d, float ca, const float* prev /* nullable */, int64_t ld_prev, float cp,
+                            const float* state_target, int64_t ld_st, float* loss /*[B+1]*/,
+                            float* state_err /*[B+1] or null without a state part*/, int64_t* count /*[B+1]*/, void* workspace,
+                            size_t ws_bytes, void* stream);
+int hgn_frame_losses_ragged_bwd(const float* net_out, int64_t ld_out, const float* target, int64_t ld_tgt, int F,
+                                const int64_t* node_type, int64_t ldt, uint32_t free_mask, int64_t rows,
+                                const int64_t* frame_rows /*host [B]*/, const int32_t* frame_ptr /*device [B+1]*/, int64_t n_frames,
+                                const int64_t* count, const float* g /* nullable */, float* d_net, int64_t ld_dnet,
+                                float* d_target, int64_t ld_dtgt, void* stream);
 
 /* ---- backward of the connector's cluster mean (hierarchical_connector.py:39-45; rmp.py HierarchicalConnector.run, the line
  * `means_all = ops.aggregate([both], [(t.node_perm, t.csr.rowptr, t.csr.seg)], ('mean',))`) ----------------------------------

@@ -16,7 +16,11 @@
     `_masked_mse` and the per-frame validation_step loop against features.frame_losses and one_step_errors(batch=B), with the
     device launches of both forms (loss_timing; profiles/frame_losses_time.md).
 
-    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only | --noise | --loss]
+  * with --ragged, one batch of 8 frames of 8 different meshes (cylinder, plate): build and build + loss through the per-frame route
+    against build_graph_frames / validation_step_batch (ragged_timing; profiles/ragged_batch_time.md).  `--ragged-route per-frame`
+    runs the per-frame route alone, with calls the package had before the ragged ones: the form that also runs on an older commit.
+
+    python tools/featbench.py [--frames 50] [--no-cpu] [--batched-only | --noise | --loss | --ragged [--ragged-route both|per-frame|ragged]]
 Prints one JSON object.
 """
 import argparse
@@ -245,6 +249,88 @@ def _frame_of(trajectory, t):
     return {k: v[t] for k, v in trajectory.items()}
 
 
+RAGGED_MESHES = {'cylinder': ((40, 30), (52, 36), (36, 28), (60, 40), (44, 34), (56, 30), (38, 32), (48, 38)),
+                 'plate': ((12, 10, 4), (16, 12, 4), (10, 10, 5), (18, 12, 4), (14, 12, 4), (12, 12, 5), (16, 10, 4), (14, 10, 5))}
+
+
+def ragged_timing(routes=('per-frame', 'ragged'), rounds=20, warm=4):
+    """Build and build + loss for ONE batch of 8 frames of 8 different meshes (cylinder: 1 008 .. 2 400 nodes; plate: 540 .. 972),
+    15 message passing steps, evaluation mode:
+      * per-frame (what the package offered for mixed meshes before the ragged calls; it runs on that commit too): build = build_graph
+        per frame + a concatenation in the style of batching.batch_graphs, which itself takes graphs of one size only (ids shifted by
+        the rows before the frame, one torch.cat per field); build + loss = build_graph, expand_graph and validation_step per frame,
+        two host reads each;
+      * ragged: build = build_graph_frames; build + loss = build_graph_frames, expand_graph_frames, validation_step_batch and one copy
+        of the [B, 2] figures.
+    The routes given alternate round by round in one process; the host clock runs around a synchronised call (ms per batch: mean,
+    min, max and standard deviation over the timed rounds), and the device launches of one call are counted in a pass of their own."""
+    from hgn_amd import synthetic, system_model
+    from hgn_amd.util import EdgeSet, MultiGraph
+
+    def concat_graphs(graphs):
+        first = [0]
+        for g in graphs:
+            first.append(first[-1] + g.node_features[0].shape[0])
+        sets = [EdgeSet(name=e.name, features=torch.cat([g.edge_sets[k].features for g in graphs]),
+                        senders=torch.cat([g.edge_sets[k].senders + p for g, p in zip(graphs, first)]),
+                        receivers=torch.cat([g.edge_sets[k].receivers + p for g, p in zip(graphs, first)]))
+                for k, e in enumerate(graphs[0].edge_sets)]
+        return MultiGraph(node_features=[torch.cat([g.node_features[0] for g in graphs])], edge_sets=sets)
+    make = {'cylinder': lambda i, m: synthetic.cylinder_frame(seed=500 + i, nx=m[0], ny=m[1]),
+            'plate': lambda i, m: synthetic.plate_frame(seed=500 + i, nx=m[0], ny=m[1], nz=m[2], obstacle=(m[0] // 2, m[1] // 2, 2))}
+    classes = {'cylinder': system_model.CylinderModel, 'plate': system_model.PlateModel}
+    out = {}
+    for kind, meshes in RAGGED_MESHES.items():
+        frames = [{k: v.cuda() for k, v in make[kind](i, m).items()} for i, m in enumerate(meshes)]
+        B = len(frames)
+        model = classes[kind](dict(params('none', 16), message_passing_steps=15))
+        with torch.no_grad():
+            model.build_graph(frames[0], True)                         # the normalisers see data once
+            model.get_target(frames[0], True)
+        forms = {}
+        if 'per-frame' in routes:
+            def per_frame_build():
+                with torch.no_grad():
+                    return concat_graphs([model.build_graph(f, False) for f in frames])
+
+            def per_frame_loss():
+                return torch.tensor([list(model.validation_step(model.expand_graph(model.build_graph(f, False), 0, B, False), f))
+                                     for f in frames])
+            forms['per-frame: build_graph x B + concatenation'] = per_frame_build
+            forms['per-frame: build_graph + validation_step x B'] = per_frame_loss
+        if 'ragged' in routes:
+            def ragged_build():
+                with torch.no_grad():
+                    return model.build_graph_frames(frames, False)
+
+            def ragged_loss():
+                with torch.no_grad():
+                    flat, frame_rows = model.concat_frames(frames)
+                    graph = model.expand_graph_frames(model.build_graph_frames((flat, frame_rows), False), frame_rows, 0, B, False)
+                    return torch.stack(model.validation_step_batch(graph, flat, frame_rows), dim=1).cpu()
+            forms['ragged: build_graph_frames'] = ragged_build
+            forms['ragged: build_graph_frames + validation_step_batch'] = ragged_loss
+        row = {'frames': B, 'nodes per frame': [int(f['node_type'].shape[0]) for f in frames],
+               'edges in the union': {e.name: int(e.senders.shape[0]) for e in concat_graphs(
+                   [model.build_graph(f, False) for f in frames]).edge_sets}}
+        if len(routes) == 2:
+            a, b = forms['per-frame: build_graph + validation_step x B'](), forms['ragged: build_graph_frames + validation_step_batch']()
+            row['max relative gap of the [B, 2] figures'] = float(((a - b).abs() / a.abs()).max())
+        row['device launches per call'] = {k: _device_launches(fn) for k, fn in forms.items()}
+        ms = {k: [] for k in forms}
+        for r in range(warm + rounds):
+            for k, fn in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if r >= warm:
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+        row.update({f'{k} ms': _stats(v) for k, v in ms.items()})
+        out[kind] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=50)
@@ -252,6 +338,8 @@ def main():
     ap.add_argument('--batched-only', action='store_true', help='only the per-frame against batched build / expand comparison')
     ap.add_argument('--noise', action='store_true', help='only the training noise: one launch per batch against the torch sequence per frame')
     ap.add_argument('--loss', action='store_true', help='only the loss: the torch sequence and the per-frame validation loop against frame_losses / one_step_errors(batch)')
+    ap.add_argument('--ragged', action='store_true', help='only a batch of frames of different meshes: the per-frame route against build_graph_frames / validation_step_batch')
+    ap.add_argument('--ragged-route', choices=('both', 'per-frame', 'ragged'), default='both', help='with --ragged: the routes to time')
     a = ap.parse_args()
     from hgn_amd import features, synthetic, system_model
     from hgn_amd.normalizer import Normalizer
@@ -264,6 +352,10 @@ def main():
         return
     if a.batched_only:
         print(json.dumps({'batched builds': batched_builds()}))
+        return
+    if a.ragged:
+        routes = ('per-frame', 'ragged') if a.ragged_route == 'both' else (a.ragged_route,)
+        print(json.dumps({'ragged batch': ragged_timing(routes)}))
         return
     frames = [synthetic.flag_frame(seed=i, nx=40, ny=40) for i in range(4)]
     cells = frames[0]['cells'].cuda()
