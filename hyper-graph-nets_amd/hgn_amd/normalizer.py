@@ -27,12 +27,24 @@ class Normalizer(nn.Module):
         self._acc_sum_squared = torch.zeros(size, dtype=torch.float32, requires_grad=False).to(device)
         self._host_num_acc = 0              # host mirror of _num_accumulations: no device sync per call
 
+    # Activation checkpointing of unrolled steps (system_model._CheckpointedStep); class-level values, set on an instance for one
+    # step only, so they are in no pickle.  `record`: a list that receives (sum, sum of squares, count) as every call that accumulates
+    # normalises with them -- copies, a few numbers each.  `replay`: an iterator over such a list while the step is rebuilt -- a
+    # call that would accumulate accumulates nothing (the first pass has) and normalises with what its call in the first pass saw,
+    # also where one normaliser accumulates twice in a step, or again in a later one.
+    record = replay = None
+
     def forward(self, batched_data: Tensor, accumulate=True) -> Tensor:
         """Differentiable with respect to ``batched_data`` (features.normalize); the running statistics are constants of the
         result, so a tensor that requires grad is accumulated from its detached values."""
-        if accumulate and self._host_num_acc < self._max_accumulations:
+        stats = (self._acc_sum, self._acc_sum_squared, self._acc_count)
+        if accumulate and self.replay is not None:
+            stats = next(self.replay, stats)
+        elif accumulate and self._host_num_acc < self._max_accumulations:
             self._accumulate(batched_data.detach() if batched_data.requires_grad else batched_data)
-        return features.normalize(batched_data, self._acc_sum, self._acc_sum_squared, self._acc_count, self._eps)
+            if self.record is not None:
+                self.record.append(tuple(t.clone() for t in stats))
+        return features.normalize(batched_data, *stats, self._eps)
 
     def inverse(self, normalized_batch_data: Tensor) -> Tensor:
         return features.normalize(normalized_batch_data, self._acc_sum, self._acc_sum_squared, self._acc_count,

@@ -559,6 +559,34 @@ def discard_stale_wgrad(ctx: Optional[Context] = None) -> int:
     return n
 
 
+class nested_backward:
+    """with ops.nested_backward(ctx): <a backward pass started from inside a backward pass>   -- the supported way to run one.
+
+    A step that is rebuilt and back-propagated inside an autograd node's backward (activation checkpointing:
+    system_model._CheckpointedStep) is an engine run of its own, with its own id.  `_arm_flush` takes a task queued from another
+    run than the armed one for the start of a new step and drops what is queued, which here would be the OUTER run's tasks -- the
+    node-level weight gradients, LayerNorm slabs and slab sums of the steps behind the rebuilt one.  So the queue changes hands
+    empty: everything queued goes out on entry (the outer run's tasks, ahead of the nested run's: every target receives its
+    contributions in the order of the backward pass, last step first), the nested run arms and flushes its own, and on exit
+    whatever it left goes out as well, which also releases its slab workspaces before the next step is rebuilt.  Both flushes
+    disarm the queue (`wq_graph_task` = -1); the outer run arms it again with its next task, finding nothing to discard.  A
+    nested run that raises leaves nothing behind: its tasks are dropped (the outer run raises with it)."""
+
+    def __init__(self, ctx: Optional[Context] = None):
+        self.ctx = ctx if ctx is not None else current()
+
+    def __enter__(self):
+        flush_wgrad(self.ctx)
+        return self.ctx
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            flush_wgrad(self.ctx)
+        else:
+            discard_stale_wgrad(self.ctx)
+        return False
+
+
 def _wtask_targets(t):
     return [p for p in (t.dW, t.db) if p]
 
@@ -566,6 +594,7 @@ def _wtask_targets(t):
 def _arm_flush(c: Context, gid: int) -> None:
     if gid != c.wq_graph_task:
         # first deferred piece of THIS engine run.  Anything still queued was left by a run that raised: never launch it.
+        # (A run started inside another run's backward finds the queue empty and disarmed: nested_backward has flushed it.)
         discard_stale_wgrad(c)
         torch.autograd.Variable._execution_engine.queue_callback(lambda: flush_wgrad(c))
         c.wq_graph_task = gid

@@ -447,7 +447,7 @@ class DataParallelTrainer:
         return self.reduce_and_update(sq.detach(), out.shape[1])
 
     def step_unrolled(self, system_model, windows, n_steps: int, through_state: bool = True, is_training: bool = True,
-                      noise_draw=None, frame_ids=None):
+                      noise_draw=None, frame_ids=None, checkpoint=None):
         """One optimiser step on the loss of an ``n_steps`` rollout unrolled under autograd
         (`system_model.unrolled_training_step`, whose arguments these are) with everything `step` gives a single step: the flat
         gradient buffer the kernels accumulate into, the all-reduce, the global-mean scaling, clipping and the fused Adam.
@@ -466,8 +466,15 @@ class DataParallelTrainer:
         in later steps the plan's one launch refreshes them all before the first call and sets `plan_epoch`, after which every
         packs_of of the step -- calls 2 .. n_steps included -- finds its cached image under an unchanged key.  A plan recorded by
         `step` serves this method and the other way round (the same MLPs).
-        Out of scope: HIP-graph capture of the unrolled step; a graph balancer; meshes that differ within a batch; activation
-        checkpointing."""
+        ``checkpoint`` is handed on (None / False: the step above, launch for launch; True: activation checkpointing, see
+        `unrolled_training_step`).  The rebuilt steps run inside this step's backward pass, i.e. between ops.begin_step_packs and
+        ops.end_step_packs, with `overlap` off and the side stream set: they find the packed images of the first pass cached (a
+        plan recorded by either kind of step serves the other), their weight gradients accumulate into the flat buffer step by step
+        (ops.nested_backward: the deferred queue is flushed when a rebuilt step starts and when it ends, so slab workspaces live for
+        one step), and the one collective still follows backward().
+        Out of scope: HIP-graph capture of the unrolled step; a graph balancer; meshes that differ within a batch."""
+        if checkpoint is not None and not isinstance(checkpoint, bool):
+            raise TypeError(f'step_unrolled: checkpoint must be None, False or True, not {checkpoint!r}')
         if getattr(system_model, 'learned_model', None) is not self.model:
             raise ValueError('step_unrolled: system_model.learned_model is not the model this trainer was built on')
         self.fp.check_outsiders()
@@ -488,7 +495,7 @@ class DataParallelTrainer:
             if cuda:
                 ops.begin_step_packs(self.ctx)
             loss, per_step = system_model.unrolled_training_step(windows, n_steps, through_state=through_state, is_training=is_training,
-                                                                 noise_draw=noise_draw, frame_ids=frame_ids)
+                                                                 noise_draw=noise_draw, frame_ids=frame_ids, checkpoint=checkpoint)
             (loss * count).backward()           # (`count`, not the slot: the slot shares its version counter with the gradients)
         finally:
             self.overlap = overlap

@@ -8,6 +8,7 @@ for the node dynamics, and three launches per normaliser.  The mesh topology (ce
 computed once per ``cells`` tensor and reused for the whole trajectory (the reference recomputes it every frame,
 flag.py:76-78).
 """
+import contextlib
 import math
 from functools import reduce
 from typing import Dict, NamedTuple, Optional, Tuple
@@ -55,6 +56,90 @@ class LockStep(NamedTuple):
     inv_from: Optional[int]         # `inv_out` holds the inverse-normalised output columns from here on; None: not recorded
     errors: str                     # the series the recorded states are compared against
     target: str                     # the series validation_step compares the updated state against
+
+
+class _CheckpointedStep(torch.autograd.Function):
+    """One step of `unrolled_training_step(checkpoint=True)` as ONE autograd node: (model, frame, names, (W, t, n_steps, accumulate,
+    last), the frame's tensors that require grad, the network's parameters that require grad) -> (loss, next state [W*N, d]; None
+    for the last step).
+
+    Forward of a step but the last: `_unroll_step` without gradients (a Function's forward runs that way), so the kernels take their
+    inference forms and nothing of the step survives but what the node keeps: the frame -- its input state, the per-step series (views
+    of the windows; at step 0 the noised frame-0 series), the shared mesh --, the clusters the step expanded with, the statistics
+    every accumulating normaliser call normalised with (Normalizer.record: a few numbers per call) and the generator states from
+    before a step that draws (the connector's `hyper_noise`, drawn where the step accumulates).
+    Its backward: the step is rebuilt with gradients from fresh leaves of the stored state under `_rebuilding` (the first pass's
+    statistics, clusters and draws) and back-propagated at once, as an engine run of its own inside ops.nested_backward, with the
+    gradients that arrived for the loss and the next state (none for the state: `advance_state` is not run again).
+    The last step is not rebuilt: its forward runs with gradients on leaves of its own and the node keeps that graph until its
+    backward, which back-propagates it the same way and lets go of it.  (As plain autograd nodes the step's functions would hold
+    their saves -- MLPFn and EdgeBlockFn keep them on the node, not with save_for_backward -- for as long as the loss is alive,
+    i.e. under every rebuild.)
+    What a backward returns for the frame's tensors and the parameters travels on through the outer run -- which visits these nodes
+    from the last step to the first, so every target receives its contributions in the plain step's order -- and the step's
+    activations die with the call, before the step before is rebuilt.  Parameters that accumulate into a trainer's flat buffer
+    report None here, as ever."""
+    FIXED = 4                                     # arguments in front of the tensors
+
+    @staticmethod
+    def forward(ctx, model, frame, names, meta, *tensors):
+        W, t, n_steps, accumulate, last = meta
+        ctx.set_materialize_grads(False)
+        ctx.model, ctx.names, ctx.meta = model, names, meta
+        ctx.weights = tensors[len(names):]
+        if last:
+            frame = dict(frame)
+            for name in names:
+                frame[name] = frame[name].detach().requires_grad_(True)
+            with torch.enable_grad():
+                loss, _, _ = model._unroll_step(frame, W, t, n_steps, accumulate, advance=False)
+            ctx.live = ([frame[name] for name in names], loss)
+            return loss.detach(), None
+        ctx.frame = {name: x for name, x in frame.items() if name not in names}
+        ctx.save_for_backward(*tensors[:len(names)])
+        ctx.rng = (torch.get_rng_state(), torch.cuda.get_rng_state()) if accumulate and model._rmp else None
+        normalizers = model._normalizers()
+        for m in normalizers:
+            m.record = []
+        try:
+            loss, nxt, _ = model._unroll_step(frame, W, t, n_steps, accumulate, advance=True, eager=True)
+        finally:
+            ctx.statistics = [m.__dict__.pop('record') for m in normalizers]
+        ctx.clusters = (model._remote_graph._clusters, model._remote_graph._neighbors) if model._rmp else None
+        return loss, nxt
+
+    @staticmethod
+    def backward(ctx, g_loss, g_next):
+        model, (W, t, n_steps, accumulate, last) = ctx.model, ctx.meta
+        launch_ctx = model.learned_model.__dict__.get('_hgn_ctx') or ops.default_context()
+        needed = ctx.needs_input_grad[_CheckpointedStep.FIXED:]
+        grads = {}
+        if last:
+            if ctx.live is None:
+                raise RuntimeError('unrolled_training_step(checkpoint=True): the loss was back-propagated a second time; a checkpointed '
+                                   'unroll frees every step as its backward pass leaves it, so it can be differentiated once '
+                                   '(retain_graph has no effect) -- call it again, or take the plain step (checkpoint=None)')
+            (leaves, loss), ctx.live = ctx.live, None
+            inputs = leaves + list(ctx.weights)
+            wanted = [x for x, need in zip(inputs, needed) if need]
+            with ops.nested_backward(launch_ctx):
+                if g_loss is not None and wanted and loss.requires_grad:
+                    grads = dict(zip(map(id, wanted), torch.autograd.grad([loss], wanted, [g_loss], allow_unused=True)))
+                del loss
+            return (None,) * _CheckpointedStep.FIXED + tuple(grads.get(id(x)) for x in inputs)
+        frame = dict(ctx.frame)
+        for name, x in zip(ctx.names, ctx.saved_tensors):
+            frame[name] = x.detach().requires_grad_(True)
+        inputs = [frame[name] for name in ctx.names] + list(ctx.weights)
+        wanted = [x for x, need in zip(inputs, needed) if need]
+        with ops.nested_backward(launch_ctx), torch.enable_grad(), model._rebuilding(ctx.clusters, ctx.rng, ctx.statistics):
+            loss, nxt, _ = model._unroll_step(frame, W, t, n_steps, accumulate, advance=g_next is not None, refresh=False)
+            pairs = [(out, g) for out, g in ((loss, g_loss), (nxt, g_next)) if g is not None and out.requires_grad]
+            if pairs and wanted:
+                got = torch.autograd.grad([out for out, _ in pairs], wanted, [g for _, g in pairs], allow_unused=True)
+                grads = dict(zip(map(id, wanted), got))
+            del loss, nxt, pairs
+        return (None,) * _CheckpointedStep.FIXED + tuple(grads.get(id(x)) for x in inputs)
 
 
 class AbstractSystemModel(nn.Module):
@@ -314,7 +399,8 @@ class AbstractSystemModel(nn.Module):
             graph = self._remote_graph.create_graph(graph, is_training)
         return graph
 
-    def expand_graph_batch(self, graph: MultiGraphWithPos, n_graphs: int, step: int, num_steps: int, is_training: bool) -> MultiGraph:
+    def expand_graph_batch(self, graph: MultiGraphWithPos, n_graphs: int, step: int, num_steps: int, is_training: bool,
+                           refresh: bool = True) -> MultiGraph:
         """Not in the reference (which expands every frame of a batch on its own and concatenates, MeshSimulator.py:159-234):
         ``expand_graph`` for the union of ``n_graphs`` frames that build_graph_batch returns.  Without a connector the union comes
         back as a MultiGraph.  With one, remote message passing runs ONCE over the union: the cluster labels are computed as in
@@ -326,7 +412,9 @@ class AbstractSystemModel(nn.Module):
         `hyper_noise` is drawn once per call for all B*K hyper nodes.
         Out of scope: a configured graph balancer (HgnError); meshes that differ within one batch go through build_graph_frames /
         expand_graph_frames, which take no connector.  Like expand_graph, a
-        connector refuses a graph that carries position gradients unless `position_gradients` is set."""
+        connector refuses a graph that carries position gradients unless `position_gradients` is set.
+        ``refresh=False`` leaves the clusters as they are whatever ``step`` says: the rebuild of a checkpointed step
+        (`unrolled_training_step(checkpoint=True)`) expands with the clusters its first pass used."""
         if self._balancer:
             raise _lib.HgnError('expand_graph_batch: the graph balancer stage has no batched form; expand the frames one by one with '
                                 'expand_graph and batch them with batching.batch_graphs, or configure the model without a balancer')
@@ -338,7 +426,7 @@ class AbstractSystemModel(nn.Module):
                                 'positions; build the graph from tensors that do not require grad, or under torch.no_grad(), or '
                                 'configure the model without this stage.  `model.position_gradients = True` lets the graph in (labels and '
                                 'spread winners are then constants)')
-        if self._refresh_due(step, num_steps, self._rmp_frequency):
+        if refresh and self._refresh_due(step, num_steps, self._rmp_frequency):
             self._remote_graph.reset_clusters()
         return self._remote_graph.create_graph_batch(graph, int(n_graphs), is_training)
 
@@ -662,8 +750,60 @@ class AbstractSystemModel(nn.Module):
         return out
 
     # ---- training on unrolled rollouts: the W windows advance in lock step, with autograd ---------------------------------
+    def _unroll_step(self, frame: Dict, W: int, t: int, n_steps: int, accumulate: bool, advance: bool, eager: bool = False,
+                     refresh: bool = True):
+        """Step ``t`` of an unroll, the one body of `unrolled_training_step`: its plain loop, the first pass of a checkpointed step
+        and that step's rebuild all run it.  ``frame``: the W current states with the per-step series of frame t.  -> (loss, the
+        next state [W*N, d] or None without ``advance``, the state's rows [W*N, d]).  ``eager``: the network is called directly, never
+        replayed from a captured graph (a first pass runs without gradients, where `forward` would replay); ``refresh``: whether
+        expand_graph_batch may compute the clusters anew."""
+        ls = self._LOCKSTEP
+        graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate, refresh=refresh)
+        flat = self.flatten_frames(frame)
+        output = self.learned_model(graph) if eager else self(graph)
+        loss = self._training_loss(self.get_target(flat, accumulate), output, flat)
+        cur = flat[ls.state]
+        if not advance:
+            return loss, None, cur
+        nxt, _ = features.advance_state(output, self._output_normalizer, cur, ls.d, ls.ca, flat[ls.prev] if ls.prev else None,
+                                        ls.cp, flat['node_type'], ls.free_types, flat[ls.fallback] if ls.fallback else None)
+        return loss, nxt, cur
+
+    def _normalizers(self):
+        return [m for m in self.modules() if isinstance(m, Normalizer)]
+
+    @contextlib.contextmanager
+    def _rebuilding(self, clusters, rng, statistics):
+        """What the rebuild of a checkpointed step runs under, so that it sees what its first pass saw and leaves no second trace:
+        every normaliser replays (``statistics`` = per normaliser, in `_normalizers` order, what Normalizer.record collected in the first
+        pass: a call that accumulated then -- the flag's node-dynamic normaliser does on every build, the connector's intra-cluster one
+        twice in a step -- accumulates nothing now and normalises with the statistics it had then); the clusters of the first pass in
+        place (``clusters`` = the remote graph's (`_clusters`, `_neighbors`) then), put back afterwards; the generators -- ``rng`` =
+        their (CPU, device) states before the first pass, None where the step draws nothing -- replayed for the connector's
+        `hyper_noise` and left as they were found."""
+        normalizers = self._normalizers()
+        remote = self._remote_graph if self._rmp else None
+        held = (remote._clusters, remote._neighbors) if remote is not None else None
+        for m, seen in zip(normalizers, statistics):
+            m.replay = iter(seen)
+        if remote is not None:
+            remote._clusters, remote._neighbors = clusters
+        try:
+            if rng is None:
+                yield
+            else:
+                with torch.random.fork_rng(devices=[torch.cuda.current_device()]):
+                    torch.set_rng_state(rng[0])
+                    torch.cuda.set_rng_state(rng[1])
+                    yield
+        finally:
+            for m in normalizers:
+                m.__dict__.pop('replay', None)
+            if remote is not None:
+                remote._clusters, remote._neighbors = held
+
     def unrolled_training_step(self, windows: Dict[str, Tensor], n_steps: int, through_state: bool = True,
-                               is_training: bool = True, noise_draw=None, frame_ids=None) -> Tuple[Tensor, Tensor]:
+                               is_training: bool = True, noise_draw=None, frame_ids=None, checkpoint=None) -> Tuple[Tensor, Tensor]:
         """Not in the reference, which trains on single steps only: the loss of an ``n_steps`` rollout unrolled under autograd, the
         remedy for rollout drift.  ``windows`` has the layout `rollout_batch` takes -- [W, T, N, .] series with T >= n_steps,
         `cells` and a `mesh_pos` shared by all windows given once -- and also holds the per-step series `get_target` reads
@@ -688,7 +828,19 @@ class AbstractSystemModel(nn.Module):
         the batched graph, bit for bit.
         This method returns an ordinary loss for any optimiser; parallel.DataParallelTrainer.step_unrolled takes it through the
         project's own trainer (flat gradient buffer, all-reduce to the mean over all ranks' windows, `max_grad_norm`, fused Adam).
-        Out of scope: HIP-graph capture of the unrolled step; activation checkpointing; meshes that differ within a batch."""
+        ``checkpoint`` (None / False: the step above, launch for launch; anything but None or a bool: TypeError): True trades one more
+        forward per step but the last for the activations of all of them.  Steps 0 .. n_steps - 2 run without gradients (the
+        inference forms of the kernels: no z saves) and keep their input state, the frame-0 series and what replays their draws
+        (`_CheckpointedStep`); the last step runs with gradients right away, so ``n_steps`` = 1 is the plain step.  The backward pass
+        visits the steps from the last to the first, rebuilds each from its stored state, back-propagates it at once with the
+        gradient of its loss and (``through_state``) of the next state, and frees its activations before the step before it is
+        rebuilt.  Same losses (equal bits), same normaliser statistics, same generator states and clusters afterwards; gradients arrive
+        where the plain step's do, each target's contributions in the same order.  Such a loss is back-propagated once (every step is
+        freed as the backward pass leaves it; a second pass raises RuntimeError); without gradients (`torch.no_grad()`) nothing would
+        be kept anyway and the call takes the plain route.
+        Out of scope: HIP-graph capture of the unrolled step; meshes that differ within a batch."""
+        if checkpoint is not None and not isinstance(checkpoint, bool):
+            raise TypeError(f'unrolled_training_step: checkpoint must be None, False or True, not {checkpoint!r}')
         ls = self._LOCKSTEP
         n_steps = int(n_steps)
         if n_steps < 1 or any(windows[name].shape[1] < n_steps for name in (ls.state,) + ls.per_step):
@@ -709,20 +861,28 @@ class AbstractSystemModel(nn.Module):
                  ls.state: first.get(ls.state, windows[ls.state][:, 0]).to(device)}
         if ls.prev:
             frame[ls.prev] = windows[ls.prev][:, 0].to(device)
+        stored = bool(checkpoint) and n_steps > 1 and torch.is_grad_enabled()       # without gradients nothing is kept anyway: the plain route
+        if stored and not self.position_gradients and (self._rmp or not ls.differentiable) and _carries_grad(
+                *(frame.get(name) for name in (ls.state, ls.prev, ls.fallback, 'mesh_pos') if name)):
+            # (the plain step refuses this in build_graph_batch / expand_graph_batch; a first pass without gradients would not)
+            raise _lib.HgnError('unrolled_training_step: PlateModel and models with a connector are not differentiable with respect to '
+                                'positions; pass windows that do not require grad, or set `model.position_gradients = True`')
+        weights = [p for p in self.learned_model.parameters() if p.requires_grad] if stored else []
         losses = []
         for t in range(n_steps):
             for name in ls.per_step:
                 frame[name] = (first[name] if t == 0 and name in first else windows[name][:, t]).to(device)
             accumulate = bool(is_training) and t == 0
-            graph = self.expand_graph_batch(self.build_graph_batch(frame, accumulate), W, t, n_steps, accumulate)
-            flat = self.flatten_frames(frame)
-            output = self(graph)
-            losses.append(self._training_loss(self.get_target(flat, accumulate), output, flat))
+            if stored:
+                names = [name for name, x in frame.items() if _carries_grad(x)]
+                loss, nxt = _CheckpointedStep.apply(self, dict(frame), names, (W, t, n_steps, accumulate, t + 1 == n_steps),
+                                                    *(frame[name] for name in names), *weights)
+                cur = frame[ls.state]
+            else:
+                loss, nxt, cur = self._unroll_step(frame, W, t, n_steps, accumulate, advance=t + 1 < n_steps)
+            losses.append(loss)
             if t + 1 == n_steps:
                 break
-            cur = flat[ls.state]
-            nxt, _ = features.advance_state(output, self._output_normalizer, cur, ls.d, ls.ca, flat[ls.prev] if ls.prev else None,
-                                            ls.cp, flat['node_type'], ls.free_types, flat[ls.fallback] if ls.fallback else None)
             if not through_state:
                 nxt, cur = nxt.detach(), cur.detach()
             frame[ls.state] = nxt.reshape(W, N, ls.d)

@@ -14,7 +14,10 @@ forms the gradients of the initial state only (data-only backw
 With `--connector <name>` (`hyper`, `hetero`, `multi`; k-means, `--clusters` hyper nodes) the model of `--unroll` has that connector.  What
 is timed then is the method in its two modes, alternating in one process: `through_state=False` (push-forward) and, with
 `--position-gradients` (which sets `model.position_gradients = True`; a connector refuses `through_state=True` without it),
-`through_state=True`.  `--position-gradients` without a connector only sets the switch: the flag graph is differentiable either way."""
+`through_state=True`.  `--position-gradients` without a connector only sets the switch: the flag graph is differentiable either way.
+With `--unroll N --checkpoint` the tool times that step plain and with `checkpoint=True` (activation checkpointing) for
+`--unroll-windows` windows, alternating in one process, and prints ms per call, the peak of torch.cuda.max_memory_allocated() over the
+start of the call and the device launches of both routes (`checkpoint_times`; profiles/unroll_checkpoint.md)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, 'hyper-graph-nets_amd')):
@@ -127,6 +130,78 @@ def unroll_times(a):
     return res
 
 
+def _device_launches(fn):
+    """Kernel launches and device copies of one call of ``fn``, counted by torch's profiler (a profiler that fails raises)."""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
+
+
+def checkpoint_times(a):
+    """`--unroll N --checkpoint`: ONE unrolled_training_step of N steps with backward() (through_state=True, frozen statistics; with a
+    connector: push-forward, or through the state with --position-gradients) on the 40x40 flag mesh (sum/L15) for `--unroll-windows`
+    windows, plain and with checkpoint=True, alternating in one process.  Per route: ms per call (mean, min), the rise of
+    torch.cuda.max_memory_allocated() over memory_allocated() across forward + backward (the largest of the timed rounds), and the
+    device launches of one call (torch's profiler, in a pass of their own after the timed rounds)."""
+    from hgn_amd import synthetic, system_model
+    torch.manual_seed(0)
+    remote = a.connector != 'none'
+    model = system_model.FlagModel(params(a.connector, a.clusters if remote else 0, 15, 'sum'))
+    model.position_gradients = bool(a.position_gradients)
+    warm = {k: v.cuda() for k, v in synthetic.flag_frame(seed=100, nx=40, ny=40).items()}
+    with torch.no_grad():
+        model.learned_model(model.expand_graph(model.build_graph(warm, True), 0, 10 ** 9, True))
+        model.get_target(warm, True)
+    W, through = a.unroll_windows, not remote or bool(a.position_gradients)
+    frames = [[synthetic.flag_frame(seed=200 + 10 * w + t, nx=40, ny=40) for t in range(a.unroll)] for w in range(W)]
+    windows = {k: torch.stack([torch.stack([f[k] for f in row]) for row in frames]).cuda()
+               for k in ('world_pos', 'prev|world_pos', 'target|world_pos', 'node_type')}
+    windows['cells'], windows['mesh_pos'] = warm['cells'], warm['mesh_pos']
+    if a.frozen:
+        model.learned_model.requires_grad_(False)
+        for k in ('world_pos', 'prev|world_pos'):
+            leaf = windows[k][:, 0].clone().requires_grad_(True)
+            windows[k] = torch.cat([leaf.unsqueeze(1), windows[k][:, 1:]], dim=1)
+    routes = {'plain': None, 'checkpoint': True}
+    times, peaks, losses = {k: [] for k in routes}, {k: 0 for k in routes}, {}
+
+    def call(checkpoint):
+        model.zero_grad(set_to_none=True)
+        loss = model.unrolled_training_step(windows, a.unroll, through, False, checkpoint=checkpoint)[0]
+        loss.backward()
+        return loss
+    for rep in range(2 + a.unroll_repeats):                    # two warm rounds: lazy state, topology caches, workspaces
+        for name, checkpoint in routes.items():
+            model.zero_grad(set_to_none=True)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            t0 = time.perf_counter()
+            loss = call(checkpoint)
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+                peaks[name] = max(peaks[name], torch.cuda.max_memory_allocated() - base)
+            losses[name] = float(loss.detach())
+            del loss
+    res = {'n_steps': a.unroll, 'windows': W, 'nodes': 1600, 'message_passing_steps': 15, 'repeats': a.unroll_repeats,
+           'connector': a.connector, 'through_state': through, 'frozen': bool(a.frozen), 'losses': losses,
+           'losses_equal': losses['plain'] == losses['checkpoint']}
+    for name, checkpoint in routes.items():
+        res[name] = {'ms': {'mean': sum(times[name]) / len(times[name]), 'min': min(times[name])},
+                     'peak_bytes_over_start': int(peaks[name])}
+        try:
+            res[name]['device_launches'] = _device_launches(lambda: call(checkpoint))
+        except Exception as err:                                # the timings stand; the count is reported as not taken, with the reason
+            res[name]['device_launches'] = None
+            res[name]['device_launches_error'] = f'{type(err).__name__}: {err}'
+    res['ms_ratio_of_the_means'] = res['checkpoint']['ms']['mean'] / res['plain']['ms']['mean']
+    res['peak_ratio'] = res['checkpoint']['peak_bytes_over_start'] / max(1, res['plain']['peak_bytes_over_start'])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--unroll', type=int, default=0, help='time one unrolled_training_step of N steps with backward() instead')
@@ -140,9 +215,11 @@ def main():
     ap.add_argument('--nstep-batch', type=int, default=0, help='also time one n_step_computation with model.nstep_batch = M and without')
     ap.add_argument('--nstep', type=int, default=60)
     ap.add_argument('--nstep-frames', type=int, default=120)
+    ap.add_argument('--checkpoint', action='store_true',
+                    help='with --unroll: time the step plain and with checkpoint=True; peak memory and device launches of both')
     a = ap.parse_args()
     if a.unroll > 0:
-        print(json.dumps(unroll_times(a)))
+        print(json.dumps(checkpoint_times(a) if a.checkpoint else unroll_times(a)))
         return
     from hgn_amd import synthetic, system_model
     res = {}
